@@ -2,6 +2,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--preset fast|fast1024|full|paper]
                     [--frames F | --frames-total T] [--res R] [--dilations 1,25]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (driver form, one rank per GPU)
 
 `--gpus N` without a torchrun environment re-launches this script under torch.distributed.run with
@@ -21,17 +22,27 @@ when the preset has it) with the frames already resident in HBM, outputs copied 
 memory; at N > 1 shard.sharded_forward (snippet data parallel over RCCL).  value = frames processed
 by all ranks / max over ranks of the timed wall time.
 
-After the timed steps the output is validated (non-zero exit otherwise): depth finite and
-renormalised to [-1, 1], and the first snippet re-run alone (batch 1, its own 3-frame encode) must
-match the batched result within the north_star depth bound (mean |Δ| ≤ 1e-3).
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` = wall
+milliseconds per timed step).  `--dump-outputs DIR` also writes what the last timed step returned
+(input_rgb, depth_pred, depth_coaligned, snippets_<i> per dilation; at N > 1 each rank's own chunk as
+<name>.rank<r>) as DIR/<name>.npy in float32, 60 MiB in all: an output larger than its even share is
+stored as the 1-D sample at the sorted indices default_rng(0).integers(0, numel, k).  The inputs are
+synthetic and seeded, so the same arguments give the same inputs in every run and build.
 
-Extra JSON fields: `roofline` for the dominant kernel family by summed time (achieved = algorithmic
+`--full` adds the checks and figures that take runs of their own (`validation` and `cpu_baseline`
+are null in a plain run's line).  The output is validated after the timed steps (non-zero exit
+otherwise): depth finite and renormalised to [-1, 1], and the first snippet re-run alone (batch 1,
+its own 3-frame encode) must match the batched result within the north_star depth bound (mean |Δ| ≤
+1e-3); `--no-validate` skips that, `--no-cpu-baseline` the CPU leg.
+
+Extra JSON fields: `roofline` (taken inside the timed steps, so in every run) for the dominant kernel
+family by summed time (achieved = algorithmic
 FLOPs of every launch of that family in the timed steps ÷ their summed HIP-event durations, events
 recorded on the launch stream), with the fused attention reported beside it (`roofline.attention`);
 `roofline.traffic` = HBM bytes per launch of that family from the committed rocprofv3 PMC passes over
 one step of the same preset (bench_traffic.json, tools/pmc_bench.sh), beside the algorithmic
 bytes per launch (every operand read once, output written once) measured here;
-`cpu_baseline`: the CPU oracle (oracle/rd_oracle.py, fp32 PyTorch restatement of the reference
+`cpu_baseline` (with `--full`): the CPU oracle (oracle/rd_oracle.py, fp32 PyTorch restatement of the reference
 pipeline, pinned to reference golden vectors) on this host — BASELINE configs[0] (3 frames 256²),
 median of 3 after a warm-up, plus one 3-frame 768² snippet.
 """
@@ -149,6 +160,35 @@ def _pmc_traffic(preset: str, family: str):
     except (OSError, KeyError, ValueError):
         return None
     return {"bytes_per_launch": fam["bytes_per_launch"], "source": ent["source"]}
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # all the --dump-outputs arrays together (float32), under the 64 MB cap
+DUMP_SEED = 0
+
+
+def _dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each array as out_dir/<name>.npy in float32.  The budget is split evenly between the
+    arrays; one that fits its share is written whole (in its own shape), a larger one as a 1-D sample:
+    the elements at the sorted flat indices numpy.random.default_rng(DUMP_SEED).integers(0, numel, k) —
+    a function of the array's shape and the number of arrays alone, so two builds given the same
+    arguments write the same elements.  Returns {name: {"shape", "saved"}} for the result line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    k = DUMP_BUDGET_BYTES // 4 // max(len(arrays), 1)
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n <= k:
+            arr = t.detach().float().cpu().numpy()
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=k, dtype=np.int64))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        info[name] = {"shape": list(t.shape), "saved": int(arr.size)}
+    return info
 
 
 def _validate(pipe, frames_dev, noise, dil0, snippet0, depth_host, coaligned_host, whole=True) -> dict:
@@ -343,14 +383,22 @@ def main():
     # 20.9 depth frames/s vs 20.6 at 16 (16/16 had measured +4.5 % over 8/8)
     ap.add_argument("--snippet-batch", type=int, default=25)
     ap.add_argument("--vae-batch", type=int, default=75)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also validate the output (finite, range, snippet 0 re-run "
+                         "alone) and time the CPU oracle baseline; a plain run does neither")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a seeded sample "
+                         "of an output larger than its share of 60 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-768-runs", type=int, default=1)
-    ap.add_argument("--no-validate", action="store_true")
+    ap.add_argument("--no-validate", action="store_true", help="with --full: skip the output validation")
     ap.add_argument("--aligner-iters", type=int, default=2000)
     ap.add_argument("--slice-world", default=None,
                     help="e.g. 2,4,8: on ONE GPU, time each rank's share of a W-rank run (collectives as local "
                          "no-ops, shard.SliceGroup) beside the single-GPU step — not a scaling number")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.slice_world:
         sys.exit(_slice_main(a))
 
@@ -410,19 +458,27 @@ def main():
     refine = pr["refine"]
     last = {}
 
-    def step(timing=None):
+    def step(timing=None, keep=False):
+        """One forward; keep=True (the last timed step under --dump-outputs) keeps every returned array."""
         if world > 1:
             so = sharded_forward(pipe, frames, list(dil0), pr["cap"], 3, coalign, init_noise=noise, num_frames=N,
                                  to_host=True, refine_step=refine, timing=timing)
             last["depth"] = so.depth_pred
             last["coaligned"] = so.depth_coaligned
             last["snip0"] = so.snippet_rows[0][0] if rank == 0 and so.snippet_rows[0].shape[0] else None
+            if keep:
+                last["out"] = {"depth_pred": so.depth_pred, "depth_coaligned": so.depth_coaligned,
+                               **{f"snippets_{i}": r for i, r in enumerate(so.snippet_rows)}}
             return
         out = pipe.forward(frames, list(dil0), pr["cap"], [3], [1], [1], coalign, refine, 3, 6, None, False, 4,
                            False, init_noise=noise)
         last["depth"] = out.depth_pred
         last["coaligned"] = out.depth_coaligned
         last["snip0"] = out.snippet_ls[0][0]
+        if keep:
+            last["out"] = {"input_rgb": out.input_rgb, "depth_pred": out.depth_pred,
+                           "depth_coaligned": out.depth_coaligned,
+                           **{f"snippets_{i}": s for i, s in enumerate(out.snippet_ls)}}
 
     for _ in range(a.warmup):
         step()
@@ -436,7 +492,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        step(marks[i] if marks else None)
+        step(marks[i] if marks else None, keep=bool(a.dump_outputs) and i == a.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -452,8 +508,12 @@ def main():
         gathered = [None] * world
         dist.all_gather_object(gathered, per_rank)
         per_rank = gathered
+    dumped = None
+    if a.dump_outputs:  # world > 1: each rank's own frame chunk and snippet rows
+        dumped = _dump_outputs(a.dump_outputs, {k + (f".rank{rank}" if world > 1 else ""): v
+                                                for k, v in last.pop("out").items()})
     validation = None
-    if not a.no_validate:
+    if a.full and not a.no_validate:
         try:
             vframes = frames if world > 1 else frames[0]
             validation = _validate(pipe, vframes, noise, dil0, last["snip0"] if rank == 0 else None, last["depth"],
@@ -495,7 +555,7 @@ def main():
                 roof["attention"] = {"kernel": an, "achieved": round(att, 1), "peak": apk, "unit": "TFLOP/s",
                                      "frac": round(att / apk, 4)}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:  # the CPU leg is an N = 1 figure
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:  # the CPU leg is an N = 1 figure
         cpu = _cpu_baseline(a.cpu_768_runs)
     if rank == 0:
         line = {
@@ -513,6 +573,8 @@ def main():
         }
         if per_rank is not None:
             line["per_rank"] = per_rank
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": a.dump_outputs, "seed": DUMP_SEED, "arrays": dumped}
         if shared:
             line["rehearsal"] = "RDMI_BENCH_SHARED_GPU=1: all ranks on one GPU over gloo (not a scaling number)"
         print(json.dumps(line), flush=True)

@@ -306,6 +306,29 @@ def test_colorize_rejects_float64():
         Cz.colorize_depth(np.zeros((1, 4, 4)), 0.0, 1.0, device="cpu")
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files; an array within its even share of the budget is
+    written whole, a larger one as the seeded sample of its flat elements — the same elements in every
+    run, so two builds compare output for output — and all files together stay under the budget."""
+    import bench
+
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 2 * 300)  # 300 float32 per array
+    small = torch.arange(20, dtype=torch.float16).view(4, 1, 5)
+    big = torch.arange(10000, dtype=torch.float32).view(100, 100)
+    info = bench._dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench._dump_outputs(str(tmp_path / "b"), {"small": small, "big": big.clone()})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == b.dtype == np.float32
+    assert s.shape == (4, 1, 5) and np.array_equal(s, small.float().numpy())
+    assert b.shape == (300,) and info["big"] == {"shape": [100, 100], "saved": 300}
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 10000, size=300, dtype=np.int64))
+    assert np.array_equal(b, idx.astype(np.float32))  # big holds its own flat indices
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert s.nbytes + b.nbytes <= bench.DUMP_BUDGET_BYTES
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
+
+
 class _FakeAV:
     """Stand-in for PyAV (absent from the image) recording what write_video_from_numpy asks of it:
     the codec fallback, stream settings, every encoded frame and the flush."""

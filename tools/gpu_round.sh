@@ -15,6 +15,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   if fatal $rc; then exit $rc; fi
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the validated line with the CPU baseline
   timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS:-} > gpurun_out/${TAG}_bench.log 2>&1
   rc=$?
   echo "bench exit $rc"

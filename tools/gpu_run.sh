@@ -6,7 +6,7 @@
 # Steps, run in the order given, each under its own time limit, output in gpurun_out/${TAG}_<step>.*:
 #   tests    pytest -m gpu (TEST_K: a -k expression, TEST_SEL: test paths, TEST_ARGS: more options)
 #   smoke    __graft_entry__.smoke()
-#   bench    bench.py ${BENCH_ARGS} (default preset, --steps ${BENCH_STEPS:-3} --warmup 2)
+#   bench    bench.py --full ${BENCH_ARGS} (default preset, --steps ${BENCH_STEPS:-3} --warmup 2)
 #   shapes   one step with RDMI_PROF_SHAPES=1 (per-launch-shape TF/s table in the JSON line)
 #   prof     rocprofv3 --kernel-trace --stats of one bench step → ${TAG}_kernel_stats.csv
 #   pmc      FETCH_SIZE / WRITE_SIZE passes of one bench step → ${TAG}_pmc/ (tools/pmc_bench.sh)
@@ -29,7 +29,7 @@ for s in $STEPS; do
     smoke)
       hb timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1; rc=$? ;;
     bench)
-      hb timeout -k 10 ${BENCH_TIMEOUT:-500} python -u bench.py --steps ${BENCH_STEPS:-3} --warmup 2 ${BENCH_ARGS:-} \
+      hb timeout -k 10 ${BENCH_TIMEOUT:-500} python -u bench.py --full --steps ${BENCH_STEPS:-3} --warmup 2 ${BENCH_ARGS:-} \
         > gpurun_out/${TAG}_bench.log 2>&1; rc=$? ;;
     shapes)
       RDMI_PROF_SHAPES=1 hb timeout -k 10 300 python -u bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-validate \
