@@ -299,6 +299,19 @@ int rdmi_renormalize_f32(float* x, long n, const float* minmax, void* stream);
  * scatter of dilation i's slot j into row i·w_i + j of [Σw, N, P] (depth_aligner.py:169-188) —
  * coinciding rows are overwritten by the later dilation, and a layout whose rows run past Σw
  * (the reference's IndexError) is rejected with RDMI_E_ARG.
+ *
+ * Start step (since rdmi_version 2): the snippets of dilation d start every start_step[d] frames
+ * (get_snippet_indice's `stride`, rollingdepth_pipeline.py:465-502; `stride` here stays the frame step
+ * INSIDE a snippet, the dilation).  With win = (w_d − 1)·stride_d + 1 and last = seq_len − win, snippet k
+ * starts at frame min(k·start_step, last) and n_d = last / start_step + 1, plus 1 when start_step does
+ * not divide last (the reference appends the last window) — csrc/aligner_index.h.  start_step 0 means 1.
+ * With every start step 1 the calls run the kernels of version 1 unchanged.  Only when some start step
+ * is > 1 is the layout checked, before any launch: a negative start step, seq_len < win or an n_d other
+ * than the count above → RDMI_E_ARG with a rdmi_last_error text.  The loss still means over the full
+ * [Σw, seq_len, P] tensor.  Such a job runs the three- or the two-launch loop: under
+ * RDMI_ALIGNER_FUSED=2 (the opt-in persistent loop) it takes the two-launch loop, and
+ * rdmi_aligner_workspace sizes the workspace for the loop that will run.  The sharded merge calls
+ * (partial_window / finish_pieces) are start step 1 only.
  */
 typedef struct rdmi_aligner_args {
   int n_dil;                 /* number of dilations (≤ 8) */
@@ -311,6 +324,7 @@ typedef struct rdmi_aligner_args {
   int iters;
   float* history;            /* [iters][3] (loss, min summ, max summ) or NULL */
   float* workspace;          /* ≥ rdmi_aligner_workspace(...) floats */
+  int start_step[8];         /* frames between snippet starts per dilation (0 = 1; see above) */
 } rdmi_aligner_args;
 long rdmi_aligner_workspace(const rdmi_aligner_args* a);
 /* Adam loop of DepthAligner.optimize (:123-229) fully on device, no host sync. */
@@ -329,6 +343,11 @@ int rdmi_aligner_prepare(const void* x, int x_f32, int n, int w, int H, int W, i
 int rdmi_aligner_merge(int n_dil, const void* const* xf, int x_f32, const float* const* s,
                        const float* const* t, const int* n, const int* stride, const int* w, int seq_len,
                        long HW, const float* shift, float* out, void* stream);
+/* rdmi_aligner_merge for snippets that start every start_step[d] frames (see the start-step note
+ * above; all ones: exactly rdmi_aligner_merge). */
+int rdmi_aligner_merge_strided(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                               const float* const* t, const int* n, const int* stride, const int* start_step,
+                               const int* w, int seq_len, long HW, const float* shift, float* out, void* stream);
 
 /* Sharded merge over frame windows: each rank sums s·x+t of ITS full-resolution
  * snippets — rows k0[d] .. k0[d]+nloc[d]-1 of dilation d, xf_d [nloc_d][w_d][HW] — over only frames

@@ -59,6 +59,7 @@ class AlignerArgs(C.Structure):
         ("depth_w", f32), ("loss_scale", f32),
         ("iters", i32),
         ("history", vp), ("workspace", vp),
+        ("start_step", i32 * 8),
     ]
 
 
@@ -102,6 +103,8 @@ _SIGS = {
     "rdmi_aligner_prepare": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "rdmi_aligner_merge": (i32, [i32, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32),
                                  C.POINTER(i32), C.POINTER(i32), i32, i64, vp, vp, vp]),
+    "rdmi_aligner_merge_strided": (i32, [i32, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32),
+                                         C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i64, vp, vp, vp]),
     "rdmi_groupnorm_affine": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "rdmi_aligner_merge_partial_window": (i32, [i32, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp),
                                                 C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),

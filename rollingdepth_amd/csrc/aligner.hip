@@ -22,10 +22,20 @@
 // value overwrites the earlier one's at every frame both cover (B stays 1; the overwritten slot
 // gets no gradient).  With one length for all dilations the rows are disjoint and the loops below
 // reduce to the plain per-dilation, per-slot order.
+//
+// Start steps (get_snippet_indice's `stride`, rollingdepth_pipeline.py:465-502): the snippets of a
+// dilation may start every ss frames plus the last window instead of at every frame.  The reference's
+// optimize / merge_scaled_triplets take explicit index tensors, so the arithmetic above is unchanged;
+// only "snippet k starts at frame k" becomes the map of aligner_index.h (integer, block-uniform,
+// outside the pixel loops).  The kernels that derive frames are templated on SS; the SS = false
+// instantiations are the start-step-1 kernels with their launch geometry and float operation order,
+// and a job whose start steps are all 1 runs only those.  The loss denominator stays Σw · N · P.
+// The persistent loop and the sharded merge (cover_count) are start-step-1 only.
 #pragma clang fp contract(off)
 #include <type_traits>
 
 #include "common.h"
+#include "aligner_index.h"
 
 namespace {
 
@@ -42,6 +52,7 @@ struct AlP {
   float* t[MAXD];
   int n[MAXD], stride[MAXD], off[MAXD];  // off: first global snippet index of dilation d
   int w[MAXD], rb[MAXD];                 // snippet length, first row (d·w_d) of dilation d
+  int ss[MAXD], last[MAXD];              // start step, start of the last window (aligner_index.h)
   int nd, R, N;                          // R = Σ w_d rows
   long P;
   float lr, b1, b2, eps, lmda2, lmda3, dw, ls;
@@ -75,11 +86,15 @@ __device__ __forceinline__ long chunk_lo(long P, int c) { return P * c / PS; }
 
 // The (dilation, snippet) whose slot holds row r of frame f in the reference's scatter (the LAST
 // dilation writing that position), or d = -1 when no dilation covers it.
+// SS: some dilation's snippets start more than one frame apart (start step > 1): snippet k starts at
+// rdmi_snip_start(k) instead of frame k.  The SS = false instantiations are the start-step-1 kernels.
+template <bool SS>
 __device__ __forceinline__ int row_owner(const AlP& p, int r, int f, int& k_out) {
   for (int d = p.nd - 1; d >= 0; --d) {
     const int j = r - p.rb[d];
     if (j < 0 || j >= p.w[d]) continue;
-    const int k = f - j * p.stride[d];
+    const int q = f - j * p.stride[d];
+    const int k = SS ? rdmi_snip_at(q, p.ss[d], p.last[d], p.n[d]) : q;
     if (k < 0 || k >= p.n[d]) continue;
     k_out = k;
     return d;
@@ -110,6 +125,7 @@ __device__ __forceinline__ void block_sums_d(double (&v)[NV]) {
 }
 
 // One (frame f, pixel chunk c) work unit of frame_stats; thread 0 returns the chunk's min/max of T.
+template <bool SS>
 __device__ __forceinline__ void frame_stats_body(const AlP& p, int f, int c, float& mn_out, float& mx_out) {
   // the slots covering frame f in row order (block-uniform): snippet row pointer, s, t — one row
   // per lane of wave 0 (R <= MAXR = 64), compacted in row order by a ballot
@@ -119,7 +135,7 @@ __device__ __forceinline__ void frame_stats_body(const AlP& p, int f, int c, flo
   if (threadIdx.x < 64) {
     const int r = threadIdx.x;
     int k = 0;
-    const int d = r < p.R ? row_owner(p, r, f, k) : -1;
+    const int d = r < p.R ? row_owner<SS>(p, r, f, k) : -1;
     const unsigned long long m = __ballot(d >= 0);
     if (d >= 0) {
       const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
@@ -201,10 +217,11 @@ __device__ __forceinline__ void frame_stats_body(const AlP& p, int f, int c, flo
   }
 }
 
+template <bool SS>
 __global__ __launch_bounds__(256) void frame_stats(AlP p) {
   const int f = blockIdx.x, c = blockIdx.y;
   float mn, mx;
-  frame_stats_body(p, f, c, mn, mx);
+  frame_stats_body<SS>(p, f, c, mn, mx);
   if (threadIdx.x == 0) {
     double* o = p.fpart + ((long)f * PS + c) * 4;
     o[2] = mn;
@@ -226,7 +243,7 @@ __device__ __forceinline__ void frame_scales(const AlP& p, int f, float& sc, flo
 // One (global snippet gk, pixel chunk c) work unit of snippet_grad; the loss partials go to
 // l1o[gk·PS + c], l2o[gk·PS + c].  COHERENT: the gradient partials are stored as agent-scope atomics
 // (device-coherent, read by another workgroup in the same launch).
-template <bool COHERENT>
+template <bool COHERENT, bool SS>
 __device__ __forceinline__ void snippet_grad_body(const AlP& p, int gk, int c, double* l1o, double* l2o) {
   const long p0 = chunk_lo(p.P, c), p1 = chunk_lo(p.P, c + 1);
   int d = 0;
@@ -236,9 +253,9 @@ __device__ __forceinline__ void snippet_grad_body(const AlP& p, int gk, int c, d
   const float* x = p.x[d] + (long)k * p.w[d] * p.P;
   double gs = 0.0, gt = 0.0, l1 = 0.0, l2 = 0.0;
   for (int j = 0; j < p.w[d]; ++j) {
-    const int f = k + j * p.stride[d];
+    const int f = (SS ? rdmi_snip_start(k, p.ss[d], p.last[d]) : k) + j * p.stride[d];
     int kk = 0;
-    if (row_owner(p, p.rb[d] + j, f, kk) != d) continue;  // overwritten by a later dilation's slot
+    if (row_owner<SS>(p, p.rb[d] + j, f, kk) != d) continue;  // overwritten by a later dilation's slot
     const float* Tf = p.T + (long)f * p.P;
     const float* Tdf = p.Td + (long)f * p.P;
     // UP pixels per thread per round: the round's operand loads and the frame's scale partials are
@@ -294,8 +311,9 @@ __device__ __forceinline__ void snippet_grad_body(const AlP& p, int gk, int c, d
   }
 }
 
+template <bool SS>
 __global__ __launch_bounds__(256) void snippet_grad(AlP p) {
-  snippet_grad_body<false>(p, blockIdx.x, blockIdx.y, p.l1, p.l2);
+  snippet_grad_body<false, SS>(p, blockIdx.x, blockIdx.y, p.l1, p.l2);
 }
 
 // Loss-history row of iteration `step` (the closure's loss.item(), summ.min(), summ.max(), :213) from
@@ -415,12 +433,13 @@ __global__ __launch_bounds__(256) void adam_step(AlP p, int step, double denom) 
 // and, in frame_stats, chunk min/max (hmm) go to per-iteration slots, and aligner_history turns
 // each block of HBLK iterations into rows.  Same arithmetic in the same order as snippet_grad + adam_step: bitwise the
 // same results (tests/test_aligner_gpu.py::test_aligner_fused_loop_bitwise).
+template <bool SS>
 __global__ __launch_bounds__(256) void snippet_grad_adam(AlP p, int it, long slot, double denom, unsigned* cnt,
                                                          double* hl, float* hst) {
   const long nps = (long)p.ntot * PS;
   const int gk = blockIdx.x;
   double* l1o = hl ? hl + slot * 2 * nps : p.l1;
-  snippet_grad_body<true>(p, gk, blockIdx.y, l1o, l1o + nps);
+  snippet_grad_body<true, SS>(p, gk, blockIdx.y, l1o, l1o + nps);
   // Hand-off without cache maintenance (see above): the partials were stored as agent-scope atomics
   // by thread 0, which waits for their completion (vmcnt) before it arrives; the last arriver reads
   // them the same way.
@@ -439,10 +458,11 @@ __global__ __launch_bounds__(256) void snippet_grad_adam(AlP p, int it, long slo
   if (threadIdx.x == 0) cnt[gk] = 0u;  // re-armed for the next iteration (next launch)
 }
 
+template <bool SS>
 __global__ __launch_bounds__(256) void frame_stats_hist(AlP p, float* hmm) {
   const int f = blockIdx.x, c = blockIdx.y;
   float mn, mx;
-  frame_stats_body(p, f, c, mn, mx);
+  frame_stats_body<SS>(p, f, c, mn, mx);
   if (hmm && threadIdx.x == 0) {
     hmm[((long)f * PS + c) * 2] = mn;
     hmm[((long)f * PS + c) * 2 + 1] = mx;
@@ -654,7 +674,7 @@ __global__ __launch_bounds__(PT, 1) void aligner_persist_k(AlP p, PerP q) {
   if (tid < 64) {
     const int r = tid;
     int k = 0;
-    const int d = r < p.R ? row_owner(p, r, f, k) : -1;
+    const int d = r < p.R ? row_owner<false>(p, r, f, k) : -1;
     const unsigned long long m = __ballot(d >= 0);
     const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
     if (d >= 0 && slot < PCM) {
@@ -790,7 +810,7 @@ __global__ __launch_bounds__(PT, 1) void aligner_persist_k(AlP p, PerP q) {
       double gsum = 0.0;
       for (int j = 0; j < p.w[d]; ++j) {
         int kk = 0;
-        if (row_owner(p, p.rb[d] + j, k + j * p.stride[d], kk) != d) continue;  // overwritten slot: no term
+        if (row_owner<false>(p, p.rb[d] + j, k + j * p.stride[d], kk) != d) continue;  // overwritten slot: no term
 #pragma unroll
         for (int h2 = 0; h2 < H; ++h2)
           gsum += __hip_atomic_load(pb + (((long)gk * q.wmax + j) * H + h2) * 2 + (is_t ? 1 : 0), __ATOMIC_RELAXED,
@@ -903,6 +923,7 @@ struct MergeP {
   const float* t[MAXD];
   int n[MAXD], stride[MAXD], w[MAXD];
   int k0[MAXD], nloc[MAXD];  // rows of x[d] are global snippets k0[d] .. k0[d]+nloc[d]-1
+  int ss[MAXD], last[MAXD];  // start step, start of the last window (aligner_index.h; merge_k<true> only)
   int nd, xf32;
   int sum_only;              // 1: write the per-frame f64 sum (sharded merge) to dsum, 0: the mean to out
   int f0;                    // first frame of out (out rows are frames f0 .. f0+gridDim.y-1)
@@ -929,6 +950,7 @@ __device__ __forceinline__ int cover_count(const int* n, const int* stride, int 
 // rounding cases), so it does not depend on the order the terms are added in — the sharded merge (per-rank window sums, all-to-all, pieces added per frame, finish)
 // gives bitwise the single-GPU result, and both round once, at the mean.  The f16-emulating mode 0
 // (the reference's fp16 merge, RDMI_MERGE_F32=0) keeps its f32 running sum.
+template <bool SS>
 __global__ void merge_k(MergeP p) {
   const int f = p.f0 + blockIdx.y;
   const float sh = p.shift ? p.shift[0] : 0.f;
@@ -938,7 +960,8 @@ __global__ void merge_k(MergeP p) {
     int cnt = 0;
     for (int d = 0; d < p.nd; ++d) {
       for (int j = p.w[d] - 1; j >= 0; --j) {  // boolean-mask order over [n_d, w]: k ascending
-        int k = f - j * p.stride[d];
+        const int q = f - j * p.stride[d];
+        int k = SS ? rdmi_snip_at(q, p.ss[d], p.last[d], p.n[d]) : q;
         if (k < p.k0[d] || k >= p.k0[d] + p.nloc[d]) continue;
         long off = ((long)(k - p.k0[d]) * p.w[d] + j) * p.HW + px;
         float a;
@@ -1034,10 +1057,12 @@ int loop_mode() {
 // ((iters + 1)·2 doubles); with a history, the
 // fused loop's per-iteration slots for min(iters, HBLK) iterations: loss partials (2·ntot·PS
 // doubles), chunk min/max (2·N·PS) and pre-update parameters (2·ntot).
-long ws_floats(int N, long P, int ntot, int iters, bool hist, int wmax) {
+long ws_floats(int N, long P, int ntot, int iters, bool hist, int wmax, bool strided) {
   long f = 8L * ntot * PS + 8L * N * PS + 2L * N * P + 4L * ntot + ((ntot + 1) & ~1L) + 4L * (iters + 1);
   // the persistent loop (opt-in, loop_mode 2): partials (2 parities), barrier words, per-iteration history
-  if (loop_mode() == 2) f += 16L * ntot * wmax + 2 + (hist ? 10L * iters * N + 2L * iters * ntot : 0);  // H <= 2
+  // (a job with a start step > 1 takes the two-launch loop under loop_mode 2: nothing reserved)
+  if (loop_mode() == 2 && !strided)
+    f += 16L * ntot * wmax + 2 + (hist ? 10L * iters * N + 2L * iters * ntot : 0);  // H <= 2
   const long slots = iters < HBLK ? iters : HBLK;
   if (hist) f += slots * (4L * ntot * PS + 2L * N * PS + 2L * ntot) + 2;
   return f + 64;
@@ -1069,6 +1094,35 @@ int aligner_persist_upt(const AlP& p, int iters) {
   return u <= 2 ? 2 : u <= 4 ? 4 : 6;  // 6: 123 VGPRs at 16 waves per CU, no spill (8 spills)
 }
 
+bool any_start_step(int nd, const int* start_step) {
+  for (int d = 0; start_step && d < nd && d < MAXD; ++d)
+    if (start_step[d] > 1) return true;
+  return false;
+}
+
+// The start steps of a job (NULL or 0: 1) → ss[d], last[d]; *strided: some start step is > 1.  Only then
+// is the snippet layout checked against the index map (aligner_index.h), before any launch: every start
+// step ≥ 0, a window fits the N frames, n[d] is the count the map gives.
+int start_steps(const char* what, int nd, const int* start_step, const int* n, const int* stride, const int* w, int N,
+                int* ss, int* last, bool* strided) {
+  *strided = any_start_step(nd, start_step);
+  for (int d = 0; d < nd; ++d) {
+    const int v = start_step ? start_step[d] : 1;
+    RDMI_REQUIRE(v >= 0, RDMI_E_ARG, "%s: start step %d of dilation %d", what, v, d);
+    ss[d] = v ? v : 1;
+    last[d] = rdmi_snip_last(N, w[d], stride[d]);
+    if (!*strided) continue;
+    RDMI_REQUIRE(stride[d] >= 1 && w[d] >= 1 && last[d] >= 0, RDMI_E_ARG,
+                 "%s: dilation %d: a snippet of length %d and frame stride %d does not fit %d frames", what, d, w[d],
+                 stride[d], N);
+    const int want = rdmi_snip_count(last[d], ss[d]);
+    RDMI_REQUIRE(n[d] == want, RDMI_E_ARG,
+                 "%s: dilation %d: %d snippets, but start step %d over %d frames (length %d, frame stride %d) gives %d",
+                 what, d, n[d], ss[d], N, w[d], stride[d], want);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" long rdmi_aligner_workspace(const rdmi_aligner_args* a) {
@@ -1076,7 +1130,8 @@ extern "C" long rdmi_aligner_workspace(const rdmi_aligner_args* a) {
   for (int d = 0; d < a->n_dil; ++d) ntot += a->n[d];
   int wmax = 1;
   for (int d = 0; d < a->n_dil; ++d) wmax = a->w[d] > wmax ? a->w[d] : wmax;
-  return ws_floats(a->seq_len, a->P, ntot, a->iters, a->history != nullptr, wmax);
+  return ws_floats(a->seq_len, a->P, ntot, a->iters, a->history != nullptr, wmax,
+                   any_start_step(a->n_dil, a->start_step));
 }
 
 extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
@@ -1102,6 +1157,9 @@ extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
     p.R += a->w[d];
   }
   RDMI_REQUIRE(p.R <= MAXR, RDMI_E_ARG, "aligner_optimize: %d rows (at most %d)", p.R, MAXR);
+  bool strided = false;
+  if (int rc = start_steps("aligner_optimize", p.nd, a->start_step, p.n, p.stride, p.w, p.N, p.ss, p.last, &strided))
+    return rc;
   for (int d = 0; d < p.nd; ++d) {
     p.rb[d] = d * p.w[d];  // the reference's torch.arange(i * w, (i + 1) * w), depth_aligner.py:182-188
     RDMI_REQUIRE(a->iters == 0 || p.rb[d] + p.w[d] <= p.R, RDMI_E_ARG,
@@ -1133,7 +1191,8 @@ extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
   if (rc) return rc;
   int wmax = 1;
   for (int d = 0; d < p.nd; ++d) wmax = p.w[d] > wmax ? p.w[d] : wmax;
-  const int mode = loop_mode();
+  // a job with a start step > 1 takes the two-launch loop where the persistent one was asked for
+  const int mode = loop_mode() == 2 && strided ? 1 : loop_mode();
   PerP q{};
   q.iters = a->iters;
   q.wmax = wmax;
@@ -1197,9 +1256,14 @@ extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
     int it0 = 1;  // first iteration whose history slots are not yet turned into rows
     for (int it = 1; it <= a->iters; ++it) {
       const long slot = (it - 1) % HBLK;
-      hipLaunchKernelGGL(frame_stats_hist, dim3(p.N, PS), dim3(256), 0, st, p,
-                         hmm ? hmm + slot * 2 * p.N * PS : nullptr);
-      hipLaunchKernelGGL(snippet_grad_adam, dim3(ntot, PS), dim3(256), 0, st, p, it, slot, denom, cnt, hl, hst);
+      float* hmms = hmm ? hmm + slot * 2 * p.N * PS : nullptr;
+      if (strided) {
+        hipLaunchKernelGGL(frame_stats_hist<true>, dim3(p.N, PS), dim3(256), 0, st, p, hmms);
+        hipLaunchKernelGGL(snippet_grad_adam<true>, dim3(ntot, PS), dim3(256), 0, st, p, it, slot, denom, cnt, hl, hst);
+      } else {
+        hipLaunchKernelGGL(frame_stats_hist<false>, dim3(p.N, PS), dim3(256), 0, st, p, hmms);
+        hipLaunchKernelGGL(snippet_grad_adam<false>, dim3(ntot, PS), dim3(256), 0, st, p, it, slot, denom, cnt, hl, hst);
+      }
       rc = rdmi::check_launch("aligner_iteration");
       if (rc) return rc;
       if (p.hist && (it - it0 + 1 == HBLK || it == a->iters)) {
@@ -1213,8 +1277,13 @@ extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
     return 0;
   }
   for (int it = 1; it <= a->iters; ++it) {
-    hipLaunchKernelGGL(frame_stats, dim3(p.N, PS), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(snippet_grad, dim3(ntot, PS), dim3(256), 0, st, p);
+    if (strided) {
+      hipLaunchKernelGGL(frame_stats<true>, dim3(p.N, PS), dim3(256), 0, st, p);
+      hipLaunchKernelGGL(snippet_grad<true>, dim3(ntot, PS), dim3(256), 0, st, p);
+    } else {
+      hipLaunchKernelGGL(frame_stats<false>, dim3(p.N, PS), dim3(256), 0, st, p);
+      hipLaunchKernelGGL(snippet_grad<false>, dim3(ntot, PS), dim3(256), 0, st, p);
+    }
     hipLaunchKernelGGL(adam_step, dim3(1), dim3(256), 0, st, p, it, denom);
     rc = rdmi::check_launch("aligner_iteration");
     if (rc) return rc;
@@ -1237,7 +1306,8 @@ extern "C" int rdmi_aligner_prepare(const void* x, int x_f32, int n, int w, int 
 
 static int merge_launch(int n_dil, const void* const* xf, int x_f32, const float* const* s, const float* const* t,
                         const int* n, const int* stride, const int* k0, const int* nloc, const int* w, int f0, int nf,
-                        long HW, const float* shift, float* out, double* dsum, void* stream) {
+                        long HW, const float* shift, float* out, double* dsum, void* stream,
+                        const int* start_step = nullptr, int seq_len = 0) {
   RDMI_REQUIRE(n_dil >= 1 && n_dil <= MAXD && (out || dsum) && HW > 0 && nf >= 0 && f0 >= 0, RDMI_E_ARG,
                "aligner_merge: bad args");
   MergeP p{};
@@ -1256,10 +1326,18 @@ static int merge_launch(int n_dil, const void* const* xf, int x_f32, const float
   }
   p.nd = n_dil; p.xf32 = x_f32; p.HW = HW; p.shift = shift; p.out = out; p.dsum = dsum;
   p.sum_only = dsum != nullptr; p.f0 = f0;
+  bool strided = false;
+  if (start_step)
+    if (int rc = start_steps("aligner_merge_strided", n_dil, start_step, p.n, p.stride, p.w, seq_len, p.ss, p.last,
+                             &strided))
+      return rc;
   if (nf == 0) return 0;
   long gx = (HW + 255) / 256;
   if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(merge_k, dim3((unsigned)gx, nf), dim3(256), 0, (hipStream_t)stream, p);
+  if (strided)
+    hipLaunchKernelGGL(merge_k<true>, dim3((unsigned)gx, nf), dim3(256), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(merge_k<false>, dim3((unsigned)gx, nf), dim3(256), 0, (hipStream_t)stream, p);
   return rdmi::check_launch("aligner_merge");
 }
 
@@ -1269,6 +1347,15 @@ extern "C" int rdmi_aligner_merge(int n_dil, const void* const* xf, int x_f32, c
   RDMI_REQUIRE(out, RDMI_E_ARG, "aligner_merge: null out");
   return merge_launch(n_dil, xf, x_f32, s, t, n, stride, nullptr, nullptr, w, 0, seq_len, HW, shift, out, nullptr,
                       stream);
+}
+
+extern "C" int rdmi_aligner_merge_strided(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                                          const float* const* t, const int* n, const int* stride,
+                                          const int* start_step, const int* w, int seq_len, long HW,
+                                          const float* shift, float* out, void* stream) {
+  RDMI_REQUIRE(out && start_step && n && stride && w, RDMI_E_ARG, "aligner_merge_strided: null argument");
+  return merge_launch(n_dil, xf, x_f32, s, t, n, stride, nullptr, nullptr, w, 0, seq_len, HW, shift, out, nullptr,
+                      stream, start_step, seq_len);
 }
 
 extern "C" int rdmi_aligner_merge_partial_window(int n_dil, const void* const* xf, int x_f32, const float* const* s,

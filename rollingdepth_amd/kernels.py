@@ -973,9 +973,17 @@ def aligner_prepare(x: torch.Tensor, shift: torch.Tensor, border: int, factor: i
 
 def aligner_optimize(xs: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], trans: Sequence[torch.Tensor],
                      strides: Sequence[int], seq_len: int, lr: float, betas, eps: float, lmda2: float, lmda3: float,
-                     depth_w: float, loss_scale: float, iters: int, history: Optional[torch.Tensor]):
+                     depth_w: float, loss_scale: float, iters: int, history: Optional[torch.Tensor],
+                     start_steps: Optional[Sequence[int]] = None):
+    """strides[d]: frame step inside a snippet of dilation d (the dilation).  start_steps[d]: frames
+    between the starts of its consecutive snippets (rdmi.h, start step; None: 1 everywhere)."""
     a = _N.AlignerArgs()
     a.n_dil = len(xs)
+    if start_steps is not None:
+        if len(start_steps) != len(xs):
+            raise ValueError(f"aligner_optimize: {len(start_steps)} start steps for {len(xs)} dilations")
+        for d, ss in enumerate(start_steps):
+            a.start_step[d] = int(ss)
     for d, (x, s, t, st) in enumerate(zip(xs, scales, trans, strides)):
         _need(x, F32, "aligner.x")
         a.x[d] = x.data_ptr()
@@ -998,9 +1006,10 @@ def aligner_optimize(xs: Sequence[torch.Tensor], scales: Sequence[torch.Tensor],
 
 
 def aligner_merge(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: int, shift: torch.Tensor,
-                  f32_arith: bool = False) -> torch.Tensor:
+                  f32_arith: bool = False, start_steps: Optional[Sequence[int]] = None) -> torch.Tensor:
     """xf[d] [n_d, w_d, H, W] (f16/f32) → [seq_len, H, W] f32.  f16 snippets are merged in the
-    reference's f16 arithmetic unless f32_arith (rdmi.h rdmi_aligner_merge x_f32 = 2)."""
+    reference's f16 arithmetic unless f32_arith (rdmi.h rdmi_aligner_merge x_f32 = 2).  start_steps:
+    frames between snippet starts per dilation (rdmi_aligner_merge_strided; None: 1 everywhere)."""
     nd = len(xf)
     H, W = xf[0].shape[-2:]
     wv = (C.c_int * nd)(*[x.shape[1] for x in xf])
@@ -1011,6 +1020,14 @@ def aligner_merge(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: i
     nn = (C.c_int * nd)(*[x.shape[0] for x in xf])
     stv = (C.c_int * nd)(*list(strides))
     mode = 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
+    if start_steps is not None:
+        if len(start_steps) != nd:
+            raise ValueError(f"aligner_merge: {len(start_steps)} start steps for {nd} dilations")
+        ssv = (C.c_int * nd)(*[int(v) for v in start_steps])
+        check(lib.rdmi_aligner_merge_strided(nd, xp, mode, sp, tp, nn, stv, ssv, wv, seq_len, H * W,
+                                             shift.data_ptr(), out.data_ptr(), _stream()),
+              "rdmi_aligner_merge_strided")
+        return out
     check(lib.rdmi_aligner_merge(nd, xp, mode, sp, tp, nn, stv, wv, seq_len, H * W,
                                  shift.data_ptr(), out.data_ptr(), _stream()), "rdmi_aligner_merge")
     return out

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import json
 import logging
+import numbers
 import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple, Union
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .aligner import DepthAligner, check_row_layout
+from .aligner import DepthAligner, check_row_layout, snippet_count, snippet_last, snippet_start
 from .config import RD_SCHEDULER, SD2_UNET, SD2_VAE
 from .scheduler import DDIMScheduler
 from .unet import UNet
@@ -573,8 +574,13 @@ class RollingDepthPipeline:
             assert len(strides) == len(dilations)
         else:
             strides = strides * len(dilations)
-        if [1] * len(dilations) != strides:
-            raise NotImplementedError("Only implemented for stride 1")
+        # one start-frame step per dilation (get_snippet_indice's `stride`; the reference's forward
+        # refuses every value but 1, rollingdepth_pipeline.py:241)
+        for s in strides:
+            if isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 1:
+                raise ValueError(f"strides must be ints >= 1, got {list(strides)}")
+        strides = [int(s) for s in strides]
+        strided = any(s != 1 for s in strides)
         seq_len = input_frames.shape[1]
         if cap_dilation:
             for i, d in enumerate(dilations):
@@ -585,9 +591,24 @@ class RollingDepthPipeline:
         # the aligner's row layout / kernel limits, before any inference (the reference fails there
         # only at its first optimisation step, after all snippets are denoised)
         check_row_layout(snippet_lengths, int((coalign_kwargs or {}).get("num_iterations", 2000)))
+        if strided:
+            # the union of all dilations' snippets must cover every frame: the reference only warns per
+            # dilation (get_snippet_indice) and its aligner then divides 0 / 0 at an uncovered frame
+            covered = set()
+            for d, w, s in zip(dilations, snippet_lengths, strides):
+                if snippet_last(seq_len, w, d) >= 0:
+                    for k in range(snippet_count(seq_len, w, d, s)):
+                        k0 = snippet_start(k, seq_len, w, d, s)
+                        covered.update(range(k0, k0 + (w - 1) * d + 1, d))
+            missing = [f for f in range(seq_len) if f not in covered]
+            if missing:
+                raise ValueError(f"strides {strides} with dilations {list(dilations)} leave frame {missing[0]} "
+                                 f"({len(missing)} of {seq_len} frames) in no snippet")
         if self._group is not None:
             import torch.distributed as dist
             if dist.get_world_size(self._group) > 1:
+                if strided:
+                    raise NotImplementedError("strides > 1 are not sharded yet")
                 return self._forward_sharded(input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs,
                                              refine_step, refine_snippet_len, refine_start_dilation, init_noise,
                                              record, generator)
@@ -613,7 +634,8 @@ class RollingDepthPipeline:
         # ----------------- co-alignment + renormalisation (:306-318)
         aligner = DepthAligner(device=self.device, verbose=verbose, **(coalign_kwargs or {}))
         merged, scales, trans, hist = aligner.run([s.view(s.shape[0], s.shape[1], 1, H, W) for s in snippets],
-                                                  dilations, merged_f32=self.merge_f32)
+                                                  dilations, strides=strides if strided else None,
+                                                  sequence_length=N if strided else None, merged_f32=self.merge_f32)
         d = merged.float().contiguous()
         K.renormalize_(d, K.minmax(d))
         coaligned = d.to(self.dtype)

@@ -1,0 +1,103 @@
+"""What snippet strides > 1 buy and cost at the fast-preset geometry (one GPU).
+
+    python tools/stride_ab.py [--rounds 3] [--frames 100] [--res 768] [--aligner-iters 2000]
+
+pipe.forward on bench.py's fast-preset workload (100 synthetic 768² frames, dilations [1, 25], f16, no
+refine, synthetic weights) with strides [1, 1], [1, 5] and [2, 5], interleaved: one warm-up of each
+variant, then `rounds` rounds of the three in turn.  Per variant: the snippet counts, the median depth
+frames/s, the run-to-run spread, the aligner time (device time of DepthAligner.run) and — as information
+only — the mean |Δ depth_pred| against the [1, 1] run of the same process (the quality cost of the knob
+on synthetic weights: no bound).  The time base is the [1, 1] run of the same interleave.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+VARIANTS = ([1, 1], [1, 5], [2, 5])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=100)
+    ap.add_argument("--res", type=int, default=768)
+    ap.add_argument("--aligner-iters", type=int, default=2000)
+    a = ap.parse_args()
+
+    from rollingdepth_amd import aligner as A
+    from rollingdepth_amd import config as C
+    from rollingdepth_amd import weights as W
+    from rollingdepth_amd.pipeline import RollingDepthPipeline
+
+    dev = torch.device("cuda", 0)
+    pipe = RollingDepthPipeline.from_synthetic(C.SD2_UNET, C.SD2_VAE, C.RD_SCHEDULER, device=dev,
+                                               torch_dtype=torch.float16)
+    frames = W.synth_frames(a.frames, a.res, a.res, seed=0)[None].to(dev, torch.float16)
+    noise = W.synth_noise(a.res // 8, a.res // 8).to(dev)
+    coalign = {"num_iterations": a.aligner_iters}
+
+    events = []
+    run0 = A.DepthAligner.run
+
+    def timed_run(self, *args, **kw):  # device time of the co-alignment (prepare, Adam loop, merge)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = run0(self, *args, **kw)
+        e1.record()
+        events.append((e0, e1))
+        return out
+
+    A.DepthAligner.run = timed_run
+
+    def one(strides):
+        events.clear()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = pipe.forward(frames, [1, 25], True, [3], [1], list(strides), coalign, 0, 3, 6, None, False, 4, False,
+                           init_noise=noise)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return dt, events[0][0].elapsed_time(events[0][1]), out
+
+    res = {tuple(v): {"s": [], "aligner_ms": []} for v in VARIANTS}
+    for v in VARIANTS:  # warm-up (and the outputs: every run of a variant computes the same values)
+        _, _, out = one(v)
+        res[tuple(v)]["counts"] = [s.shape[0] for s in out.snippet_ls]
+        res[tuple(v)]["depth"] = out.depth_pred.float()
+    for r in range(a.rounds):
+        for v in VARIANTS:
+            dt, al, _ = one(v)
+            res[tuple(v)]["s"].append(dt)
+            res[tuple(v)]["aligner_ms"].append(al)
+            print(f"round {r} strides {v}: {dt:.3f} s ({a.frames / dt:.2f} depth frames/s), aligner {al:.1f} ms",
+                  flush=True)
+    base = res[tuple(VARIANTS[0])]
+    bmed = statistics.median(base["s"])
+    print("| strides | snippets | depth frames/s (median) | min .. max | vs [1, 1] | aligner ms | mean abs Δ depth_pred |")
+    print("|---|---|---|---|---|---|---|")
+    rows = []
+    for v in VARIANTS:
+        x = res[tuple(v)]
+        med = statistics.median(x["s"])
+        fps = [a.frames / s for s in x["s"]]
+        dd = (x["depth"] - base["depth"]).abs().mean().item()
+        row = {"strides": v, "snippets": x["counts"], "frames_per_s": round(a.frames / med, 2),
+               "frames_per_s_min": round(min(fps), 2), "frames_per_s_max": round(max(fps), 2),
+               "speedup": round(bmed / med, 3), "aligner_ms": round(statistics.median(x["aligner_ms"]), 1),
+               "mean_abs_ddepth": dd}
+        rows.append(row)
+        print(f"| {v} | {' + '.join(map(str, x['counts']))} = {sum(x['counts'])} | {row['frames_per_s']:.2f} | "
+              f"{row['frames_per_s_min']:.2f} .. {row['frames_per_s_max']:.2f} | {row['speedup']:.3f}x | "
+              f"{row['aligner_ms']:.1f} | {dd:.2e} |")
+    print(json.dumps({"tool": "stride_ab", "frames": a.frames, "res": a.res, "rounds": a.rounds, "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()
