@@ -812,10 +812,15 @@ def attention_d512(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: flo
 
 
 def transpose(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """[B, R, Cc] (row stride any) → [B, Cc, R] contiguous."""
+    """[B, R, Cc] (row stride any) → [B, Cc, R] contiguous, or into `out` (row stride any).  The kernel
+    steps from image to image by rows · row stride: a view whose batch stride differs is refused."""
     _need_act(src, "transpose.src")
     B, R, Cc = src.shape
     out = torch.empty((B, Cc, R), dtype=src.dtype, device=src.device) if out is None else out
+    for t, rows, nm in ((src, R, "src"), (out, Cc, "out")):
+        if t.stride(2) != 1 or (B > 1 and t.stride(0) != rows * t.stride(1)):
+            raise ValueError(f"transpose: {nm} strides {t.stride()} (unit column stride, batch stride = rows · row "
+                             f"stride expected)")
     check(lib.rdmi_transpose(src.data_ptr(), out.data_ptr(), B, R, Cc, src.stride(1), out.stride(1), _dtype_code(src),
                              _stream()), "rdmi_transpose")
     return out
