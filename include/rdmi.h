@@ -311,7 +311,8 @@ int rdmi_renormalize_f32(float* x, long n, const float* minmax, void* stream);
  * [Σw, seq_len, P] tensor.  Such a job runs the three- or the two-launch loop: under
  * RDMI_ALIGNER_FUSED=2 (the opt-in persistent loop) it takes the two-launch loop, and
  * rdmi_aligner_workspace sizes the workspace for the loop that will run.  The sharded merge calls
- * (partial_window / finish_pieces) are start step 1 only.
+ * (partial_window / finish_pieces) keep start step 1; since rdmi_version 3 their _strided forms take the
+ * start steps, with the same check before any launch.
  */
 typedef struct rdmi_aligner_args {
   int n_dil;                 /* number of dilations (≤ 8) */
@@ -367,6 +368,21 @@ int rdmi_aligner_merge_partial_window(int n_dil, const void* const* xf, int x_f3
 int rdmi_aligner_merge_finish_pieces(int n_dil, const int* n, const int* stride, const int* w, int f0, int nf, long HW,
                                      int npieces, const int* piece_f0, const int* piece_nf, const double* recv,
                                      float* out, void* stream);
+/* The two calls above for snippets that start every start_step[d] frames of seq_len (since rdmi_version 3;
+ * see the start-step note above): k0 / nloc still count snippets, snippet k starting at frame
+ * min(k·start_step, last), and the cover count is that of the strided layout (0 at a frame no snippet
+ * reaches: out is 0 there).  The window / chunk f0 .. f0+nf-1 must lie inside the seq_len frames.  The
+ * layout is checked as in rdmi_aligner_merge_strided, RDMI_E_ARG before any launch; all-ones start steps
+ * launch exactly what the calls above launch. */
+int rdmi_aligner_merge_partial_window_strided(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                                              const float* const* t, const int* n, const int* stride,
+                                              const int* start_step, const int* k0, const int* nloc, const int* w,
+                                              int seq_len, int f0, int nf, long HW, const float* shift,
+                                              double* sum_out, void* stream);
+int rdmi_aligner_merge_finish_pieces_strided(int n_dil, const int* n, const int* stride, const int* start_step,
+                                             const int* w, int seq_len, int f0, int nf, long HW, int npieces,
+                                             const int* piece_f0, const int* piece_nf, const double* recv,
+                                             float* out, void* stream);
 
 /* Single-head flash attention for head dim 512 (f16): the VAE mid-block attention
  * (unet_2d_blocks.py:680-697 through AttnProcessor2_0's 4-D path, attention_processor.py:2172-2276 —

@@ -30,7 +30,8 @@
 // outside the pixel loops).  The kernels that derive frames are templated on SS; the SS = false
 // instantiations are the start-step-1 kernels with their launch geometry and float operation order,
 // and a job whose start steps are all 1 runs only those.  The loss denominator stays Σw · N · P.
-// The persistent loop and the sharded merge (cover_count) are start-step-1 only.
+// The persistent loop is start-step-1 only; the sharded merge takes start steps through its _strided
+// entry points (window sums: merge_k<true>; cover count: rdmi_cover_count).
 #pragma clang fp contract(off)
 #include <type_traits>
 
@@ -923,7 +924,7 @@ struct MergeP {
   const float* t[MAXD];
   int n[MAXD], stride[MAXD], w[MAXD];
   int k0[MAXD], nloc[MAXD];  // rows of x[d] are global snippets k0[d] .. k0[d]+nloc[d]-1
-  int ss[MAXD], last[MAXD];  // start step, start of the last window (aligner_index.h; merge_k<true> only)
+  int ss[MAXD], last[MAXD];  // start step, start of the last window (aligner_index.h; the SS = true kernels only)
   int nd, xf32;
   int sum_only;              // 1: write the per-frame f64 sum (sharded merge) to dsum, 0: the mean to out
   int f0;                    // first frame of out (out rows are frames f0 .. f0+gridDim.y-1)
@@ -1003,9 +1004,11 @@ struct PiecesP {
   int np;
 };
 
+template <bool SS>
 __global__ void merge_finish_pieces_k(MergeP p, PiecesP q, const double* __restrict__ recv) {
   const int fl = blockIdx.y, f = p.f0 + fl;
-  const int cnt = cover_count(p.n, p.stride, p.nd, p.w, f);
+  const int cnt = SS ? rdmi_cover_count(p.nd, p.n, p.stride, p.w, p.ss, p.last, f)
+                     : cover_count(p.n, p.stride, p.nd, p.w, f);
   for (long px = blockIdx.x * (long)blockDim.x + threadIdx.x; px < p.HW; px += (long)gridDim.x * blockDim.x) {
     double s = 0.0;
     for (int i = 0; i < q.np; ++i)
@@ -1366,13 +1369,25 @@ extern "C" int rdmi_aligner_merge_partial_window(int n_dil, const void* const* x
   return merge_launch(n_dil, xf, x_f32, s, t, n, stride, k0, nloc, w, f0, nf, HW, shift, nullptr, sum_out, stream);
 }
 
-extern "C" int rdmi_aligner_merge_finish_pieces(int n_dil, const int* n, const int* stride, const int* w, int f0,
-                                                int nf, long HW, int npieces, const int* piece_f0,
-                                                const int* piece_nf, const double* recv, float* out, void* stream) {
+extern "C" int rdmi_aligner_merge_partial_window_strided(int n_dil, const void* const* xf, int x_f32,
+                                                         const float* const* s, const float* const* t, const int* n,
+                                                         const int* stride, const int* start_step, const int* k0,
+                                                         const int* nloc, const int* w, int seq_len, int f0, int nf,
+                                                         long HW, const float* shift, double* sum_out, void* stream) {
+  RDMI_REQUIRE(k0 && nloc && sum_out && start_step && n && stride && w, RDMI_E_ARG,
+               "aligner_merge_partial_window_strided: null argument");
+  RDMI_REQUIRE(f0 >= 0 && nf >= 0 && f0 <= seq_len && nf <= seq_len - f0, RDMI_E_ARG,
+               "aligner_merge_partial_window_strided: frames %d+%d outside the %d of the sequence", f0, nf, seq_len);
+  return merge_launch(n_dil, xf, x_f32, s, t, n, stride, k0, nloc, w, f0, nf, HW, shift, nullptr, sum_out, stream,
+                      start_step, seq_len);
+}
+
+static int finish_pieces_launch(int n_dil, const int* n, const int* stride, const int* w, int f0, int nf, long HW,
+                                int npieces, const int* piece_f0, const int* piece_nf, const double* recv, float* out,
+                                void* stream, const int* start_step = nullptr, int seq_len = 0) {
   RDMI_REQUIRE(n_dil >= 1 && n_dil <= MAXD && n && stride && w && (out || nf == 0) && HW > 0 && f0 >= 0 && nf >= 0 &&
                    npieces >= 0 && (npieces == 0 || (piece_f0 && piece_nf && recv)),
                RDMI_E_ARG, "aligner_merge_finish_pieces: bad args");
-  if (nf == 0) return 0;
   MergeP p{};
   for (int d = 0; d < n_dil; ++d) {
     p.n[d] = n[d];
@@ -1380,6 +1395,12 @@ extern "C" int rdmi_aligner_merge_finish_pieces(int n_dil, const int* n, const i
     p.w[d] = w[d];
   }
   p.nd = n_dil; p.HW = HW;
+  bool strided = false;
+  if (start_step)
+    if (int rc = start_steps("aligner_merge_finish_pieces_strided", n_dil, start_step, p.n, p.stride, p.w, seq_len,
+                             p.ss, p.last, &strided))
+      return rc;
+  if (nf == 0) return 0;
   long off = 0;
   for (int i = 0; i < npieces; ++i) {
     RDMI_REQUIRE(piece_nf[i] >= 0 && piece_f0[i] >= f0 && piece_f0[i] + piece_nf[i] <= f0 + nf, RDMI_E_ARG,
@@ -1418,9 +1439,32 @@ extern "C" int rdmi_aligner_merge_finish_pieces(int n_dil, const int* n, const i
     }
     p.f0 = fs;
     p.out = out + (long)(fs - f0) * HW;
-    hipLaunchKernelGGL(merge_finish_pieces_k, dim3((unsigned)gx, fe - fs), dim3(256), 0, (hipStream_t)stream, p, q, recv);
+    if (strided)
+      hipLaunchKernelGGL(merge_finish_pieces_k<true>, dim3((unsigned)gx, fe - fs), dim3(256), 0, (hipStream_t)stream, p,
+                         q, recv);
+    else
+      hipLaunchKernelGGL(merge_finish_pieces_k<false>, dim3((unsigned)gx, fe - fs), dim3(256), 0, (hipStream_t)stream,
+                         p, q, recv);
     if (int rc = rdmi::check_launch("aligner_merge_finish_pieces")) return rc;
     fs = fe;
   }
   return 0;
+}
+
+extern "C" int rdmi_aligner_merge_finish_pieces(int n_dil, const int* n, const int* stride, const int* w, int f0,
+                                                int nf, long HW, int npieces, const int* piece_f0,
+                                                const int* piece_nf, const double* recv, float* out, void* stream) {
+  return finish_pieces_launch(n_dil, n, stride, w, f0, nf, HW, npieces, piece_f0, piece_nf, recv, out, stream);
+}
+
+extern "C" int rdmi_aligner_merge_finish_pieces_strided(int n_dil, const int* n, const int* stride,
+                                                        const int* start_step, const int* w, int seq_len, int f0,
+                                                        int nf, long HW, int npieces, const int* piece_f0,
+                                                        const int* piece_nf, const double* recv, float* out,
+                                                        void* stream) {
+  RDMI_REQUIRE(start_step, RDMI_E_ARG, "aligner_merge_finish_pieces_strided: null start_step");
+  RDMI_REQUIRE(f0 >= 0 && nf >= 0 && f0 <= seq_len && nf <= seq_len - f0, RDMI_E_ARG,
+               "aligner_merge_finish_pieces_strided: frames %d+%d outside the %d of the sequence", f0, nf, seq_len);
+  return finish_pieces_launch(n_dil, n, stride, w, f0, nf, HW, npieces, piece_f0, piece_nf, recv, out, stream,
+                              start_step, seq_len);
 }

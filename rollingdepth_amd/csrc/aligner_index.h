@@ -4,7 +4,8 @@
 //   ss      start step: frame step between consecutive snippet starts (the reference's `stride`)
 //   last    N − win, win = (w − 1)·stride + 1: the start of the last window that fits N frames
 // One definition for the device code (aligner.hip), the host-side validation and the CPU check
-// program (tests/cpp/aligner_index_check.cpp): plain integer functions, no other dependency.
+// programs (tests/cpp/aligner_index_check.cpp, cover_count_check.cpp): plain integer functions, no
+// other dependency.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -30,4 +31,14 @@ RDMI_HD int rdmi_snip_at(int q, int ss, int last, int n) {
   if (q < 0 || q > last) return -1;
   if (q == last) return n - 1;
   return q % ss == 0 ? q / ss : -1;
+}
+
+// number of (dilation, slot) pairs covering frame f over nd dilations: slot j of dilation d covers f
+// when a snippet of d starts at frame f − j·stride[d] (n[d] = rdmi_snip_count(last[d], ss[d]))
+RDMI_HD int rdmi_cover_count(int nd, const int* n, const int* stride, const int* w, const int* ss, const int* last,
+                             int f) {
+  int cnt = 0;
+  for (int d = 0; d < nd; ++d)
+    for (int j = 0; j < w[d]; ++j) cnt += rdmi_snip_at(f - j * stride[d], ss[d], last[d], n[d]) >= 0 ? 1 : 0;
+  return cnt;
 }

@@ -1038,14 +1038,29 @@ def aligner_merge(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: i
     return out
 
 
+def _start_step_array(what: str, start_steps: Optional[Sequence[int]], seq_len: Optional[int], nd: int):
+    """The start steps of a sharded-merge call as a C int array (None: the start-step-1 entry point)."""
+    if start_steps is None:
+        return None
+    if len(start_steps) != nd:
+        raise ValueError(f"{what}: {len(start_steps)} start steps for {nd} dilations")
+    if seq_len is None:
+        raise ValueError(f"{what}: start_steps need seq_len (a snippet count does not determine it)")
+    return (C.c_int * nd)(*[int(v) for v in start_steps])
+
+
 def aligner_merge_partial_window(xf: Sequence[Optional[torch.Tensor]], k0: Sequence[int], n: Sequence[int], scales,
                                  trans, strides, w: Sequence[int], f0: int, nf: int, HW: int, shift: torch.Tensor,
-                                 x_f32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                 x_f32, out: Optional[torch.Tensor] = None,
+                                 start_steps: Optional[Sequence[int]] = None,
+                                 seq_len: Optional[int] = None) -> torch.Tensor:
     """Sharded merge, rank-local half (rdmi_aligner_merge_partial_window): xf[d] [nloc_d, w_d, H, W] =
     global snippets k0[d] .. of dilation d (None / 0 rows when the rank owns none) → f64 [nf, HW] sums of
     s·x+t over frames f0 .. f0+nf-1 (a range the rank's snippets cover; `out`: a contiguous f64 [nf, HW]
-    view to write into)."""
+    view to write into).  start_steps: frames between snippet starts per dilation, with the seq_len they
+    are laid over (rdmi_aligner_merge_partial_window_strided; None: 1 everywhere)."""
     nd = len(xf)
+    ssv = _start_step_array("aligner_merge_partial_window", start_steps, seq_len, nd)
     if out is None:
         out = torch.empty((nf, HW), dtype=torch.float64, device=shift.device)
     elif out.dtype != torch.float64 or tuple(out.shape) != (nf, HW) or not out.is_contiguous():
@@ -1058,6 +1073,12 @@ def aligner_merge_partial_window(xf: Sequence[Optional[torch.Tensor]], k0: Seque
     nl = (C.c_int * nd)(*[(x.shape[0] if x is not None else 0) for x in xf])
     stv = (C.c_int * nd)(*list(strides))
     wv = (C.c_int * nd)(*list(w))
+    if ssv is not None:
+        check(lib.rdmi_aligner_merge_partial_window_strided(nd, xp, int(x_f32), sp, tp, nn, stv, ssv, kk, nl, wv,
+                                                            int(seq_len), f0, nf, HW, shift.data_ptr(),
+                                                            out.data_ptr(), _stream()),
+              "rdmi_aligner_merge_partial_window_strided")
+        return out
     check(lib.rdmi_aligner_merge_partial_window(nd, xp, int(x_f32), sp, tp, nn, stv, kk, nl, wv, f0, nf, HW,
                                                 shift.data_ptr(), out.data_ptr(), _stream()),
           "rdmi_aligner_merge_partial_window")
@@ -1065,18 +1086,32 @@ def aligner_merge_partial_window(xf: Sequence[Optional[torch.Tensor]], k0: Seque
 
 
 def aligner_merge_finish_pieces(recv: torch.Tensor, pieces: Sequence[Tuple[int, int]], n: Sequence[int],
-                                strides: Sequence[int], w: Sequence[int], f0: int, nf: int, HW: int) -> torch.Tensor:
+                                strides: Sequence[int], w: Sequence[int], f0: int, nf: int, HW: int,
+                                start_steps: Optional[Sequence[int]] = None, seq_len: Optional[int] = None,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sharded merge over frame windows, after the all-to-all: recv f64 [Σ nf_q, HW] = the pieces
-    (first frame, frame count) back to back in source-rank order → f32 [nf, HW] means of frames f0 .."""
+    (first frame, frame count) back to back in source-rank order → f32 [nf, HW] means of frames f0 ..
+    start_steps / seq_len: as aligner_merge_partial_window (rdmi_aligner_merge_finish_pieces_strided: the
+    cover count of the strided layout, 0 — and a 0 output — at a frame no snippet reaches)."""
     if recv.dtype != torch.float64:
         raise TypeError("aligner_merge_finish_pieces: f64 sums expected")
     nd, npc = len(n), len(pieces)
-    out = torch.empty((nf, HW), dtype=F32, device=recv.device)
+    ssv = _start_step_array("aligner_merge_finish_pieces", start_steps, seq_len, nd)
+    if out is None:
+        out = torch.empty((nf, HW), dtype=F32, device=recv.device)
+    elif out.dtype != F32 or tuple(out.shape) != (nf, HW) or not out.is_contiguous():
+        raise ValueError("aligner_merge_finish_pieces: out must be contiguous f32 [nf, HW]")
     nn = (C.c_int * nd)(*list(n))
     stv = (C.c_int * nd)(*list(strides))
     wv = (C.c_int * nd)(*list(w))
     pf = (C.c_int * max(npc, 1))(*[p[0] for p in pieces])
     pn = (C.c_int * max(npc, 1))(*[p[1] for p in pieces])
+    if ssv is not None:
+        check(lib.rdmi_aligner_merge_finish_pieces_strided(nd, nn, stv, ssv, wv, int(seq_len), f0, nf, HW, npc, pf, pn,
+                                                           recv.data_ptr() if recv.numel() else None,
+                                                           out.data_ptr(), _stream()),
+              "rdmi_aligner_merge_finish_pieces_strided")
+        return out
     check(lib.rdmi_aligner_merge_finish_pieces(nd, nn, stv, wv, f0, nf, HW, npc, pf, pn,
                                                recv.data_ptr() if recv.numel() else None, out.data_ptr(),
                                                _stream()), "rdmi_aligner_merge_finish_pieces")

@@ -527,10 +527,10 @@ class RollingDepthPipeline:
         return out
 
     def _forward_sharded(self, input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs, refine_step,
-                         refine_snippet_len, refine_start_dilation, init_noise, record, generator=None):
+                         refine_snippet_len, refine_start_dilation, init_noise, record, generator=None, strides=1):
         """forward() over W ranks (shard.sharded_forward), outputs assembled on every rank.  Dilations
-        arrive already capped (forward's checks ran); the snippets are all-gathered at full
-        resolution only here, to honour the snippet_ls contract (bench.py keeps them distributed)."""
+        arrive already capped and strides validated (forward's checks ran); the snippets are all-gathered
+        at full resolution only here, to honour the snippet_ls contract (bench.py keeps them distributed)."""
         import torch.distributed as dist
         from .shard import gather_rows_by_dilation, sharded_forward
 
@@ -539,7 +539,8 @@ class RollingDepthPipeline:
                              init_noise=init_noise, group=self._group, refine_step=refine_step,
                              refine_snippet_len=refine_snippet_len, refine_start_dilation=refine_start_dilation,
                              gather=True, record=record, generator=generator,
-                             init_infer_steps=list(init_infer_steps))
+                             init_infer_steps=list(init_infer_steps),
+                             strides=list(strides) if isinstance(strides, (list, tuple)) else strides)
         snips = gather_rows_by_dilation([r.to(self.dtype) for r in so.snippet_rows], so.snippet_counts, world,
                                         self._group)
         H, W = so.depth_pred_full.shape[-2:]
@@ -607,11 +608,9 @@ class RollingDepthPipeline:
         if self._group is not None:
             import torch.distributed as dist
             if dist.get_world_size(self._group) > 1:
-                if strided:
-                    raise NotImplementedError("strides > 1 are not sharded yet")
                 return self._forward_sharded(input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs,
                                              refine_step, refine_snippet_len, refine_start_dilation, init_noise,
-                                             record, generator)
+                                             record, generator, strides)
         # ----------------- encode (H2D boundary :263)
         frames = input_frames[0].to(self.device)
         # input_rgb = frames / 2 + 0.5 in f16 as the reference computes it on the host (x/2 is exact,

@@ -23,6 +23,10 @@ One process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI).  Per f
      latents are all-gathered, and every refine step splits its snippets over the ranks with one
      all-reduce of the [N, h·w, 4] f32 per-frame sums (pipeline.refine(group=...)); each rank decodes
      its own frame chunk of the refined latents.
+Snippet strides > 1 (forward()'s `strides`; `start_steps` here — `strides` in this module is the frame step
+inside a snippet, the dilation): the same plan over the strided snippet counts, with snippet k of a
+dilation starting at aligner.snippet_start(k) instead of frame k in the frame windows, the window sums
+and the cover count (csrc/aligner_index.h).
 Outputs stay distributed: rank r holds depth / coaligned depth for frames chunk_bounds(N, W)[r]
 (and its own decoded snippets); `gather=True` assembles the full maps on every rank.
 
@@ -40,6 +44,7 @@ single-GPU forward bitwise.
 from __future__ import annotations
 
 import math
+import numbers
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -217,11 +222,26 @@ def _all_reduce_minmax(mm: torch.Tensor, group=None) -> torch.Tensor:
     return torch.stack([t[0], -t[1]])
 
 
-def frame_ranges(subsets: Sequence[Sequence[int]], strides: Sequence[int], w: Sequence[int]) -> List[Tuple[int, int]]:
+def _strided(start_steps: Optional[Sequence[int]]) -> bool:
+    return start_steps is not None and any(int(s) != 1 for s in start_steps)
+
+
+def frame_ranges(subsets: Sequence[Sequence[int]], strides: Sequence[int], w: Sequence[int],
+                 start_steps: Optional[Sequence[int]] = None, N: Optional[int] = None) -> List[Tuple[int, int]]:
     """Frames a rank's snippets cover, as sorted disjoint ranges [lo, hi): slot j of snippet k of
     dilation d is frame k + j·stride_d (depth_aligner.py:179-188); one range per dilation's contiguous
-    snippet run (a dilation's frames between its slots included), overlapping ranges joined."""
-    rs = sorted((min(sub), max(sub) + (wd - 1) * st + 1) for sub, st, wd in zip(subsets, strides, w) if sub)
+    snippet run (a dilation's frames between its slots included), overlapping ranges joined.
+    start_steps (frames between snippet starts per dilation, over N frames; None or all ones: snippet k
+    starts at frame k): the run reaches from the start of its first snippet to the end of its last
+    (aligner.snippet_start — the appended last window included)."""
+    if _strided(start_steps):
+        from .aligner import snippet_start
+        if N is None or len(start_steps) != len(strides):
+            raise ValueError(f"start steps {list(start_steps)} need N and one entry per dilation ({len(strides)})")
+        rs = sorted((snippet_start(min(sub), N, wd, st, ss), snippet_start(max(sub), N, wd, st, ss) + (wd - 1) * st + 1)
+                    for sub, st, wd, ss in zip(subsets, strides, w, start_steps) if sub)
+    else:
+        rs = sorted((min(sub), max(sub) + (wd - 1) * st + 1) for sub, st, wd in zip(subsets, strides, w) if sub)
     out: List[Tuple[int, int]] = []
     for lo, hi in rs:
         if out and lo <= out[-1][1]:
@@ -237,39 +257,42 @@ def _cut(ranges: Sequence[Tuple[int, int]], lo: int, hi: int) -> List[Tuple[int,
 
 
 def merge_exchange_plan(counts: Sequence[int], strides: Sequence[int], w: Sequence[int], N: int, world: int,
-                        rank: int):
+                        rank: int, start_steps: Optional[Sequence[int]] = None):
     """The all-to-all of the windowed merge, from the plan alone (no communication): this rank's
     frame ranges, the rows it sends to each rank (its rows inside that rank's frame chunk — the
     ranges' rows are stored in frame order, so each destination's rows are contiguous) and the pieces
     (first frame, frame count) it receives from each rank (the sender's ranges cut by this rank's
-    chunk, in frame order)."""
-    ranges = [frame_ranges(rank_subsets(counts, world, r), strides, w) for r in range(world)]
+    chunk, in frame order).  start_steps: as frame_ranges (counts are then the strided counts)."""
+    ranges = [frame_ranges(rank_subsets(counts, world, r), strides, w, start_steps, N) for r in range(world)]
     chunks = chunk_bounds(N, world)
     send = [sum(m for _, m in _cut(ranges[rank], *chunks[r])) for r in range(world)]
     recv = [_cut(ranges[r], *chunks[rank]) for r in range(world)]
     return ranges[rank], send, recv
 
 
-def _merge_windowed(rows, k0, counts, scales, trans, strides, slens, N: int, HW: int, shift, x_f32, group):
+def _merge_windowed(rows, k0, counts, scales, trans, strides, slens, N: int, HW: int, shift, x_f32, group,
+                    start_steps: Optional[Sequence[int]] = None):
     """merge_scaled_triplets over W ranks: per-rank f64 sums of only the frames its snippets cover, an
     all-to-all of the rows each rank's frame chunk needs (uneven row counts; RCCL over xGMI), then
     the received pieces added per frame in source-rank order and ÷ the cover count (f64 sums: the
     single-GPU merge bitwise).  Returns this rank's chunk
-    [f1 − f0, HW] f32.  Moves each rank's covered frames instead of N·HW·8 B per rank."""
+    [f1 − f0, HW] f32.  Moves each rank's covered frames instead of N·HW·8 B per rank.
+    start_steps (None or all ones: the start-step-1 calls): frames between snippet starts per dilation."""
     from . import kernels as K
 
     world, rank = _world(group), _rank(group)
-    ranges, send, recv = merge_exchange_plan(counts, strides, slens, N, world, rank)
+    ss = dict(start_steps=list(start_steps), seq_len=N) if _strided(start_steps) else {}
+    ranges, send, recv = merge_exchange_plan(counts, strides, slens, N, world, rank, start_steps)
     f0, f1 = chunk_bounds(N, world)[rank]
     sums = torch.empty((sum(b - a for a, b in ranges), HW), dtype=torch.float64, device=shift.device)
     o = 0
     for a, b in ranges:
         K.aligner_merge_partial_window([r if r.shape[0] else None for r in rows], k0, counts, scales, trans,
-                                       strides, slens, a, b - a, HW, shift, x_f32, out=sums[o:o + b - a])
+                                       strides, slens, a, b - a, HW, shift, x_f32, out=sums[o:o + b - a], **ss)
         o += b - a
     rbuf = exchange_window_rows(sums, send, [sum(m for _, m in pc) for pc in recv], group)
     pieces = [pc for src in recv for pc in src]
-    return K.aligner_merge_finish_pieces(rbuf, pieces, counts, strides, slens, f0, f1 - f0, HW)
+    return K.aligner_merge_finish_pieces(rbuf, pieces, counts, strides, slens, f0, f1 - f0, HW, **ss)
 
 
 def exchange_window_rows(sums: torch.Tensor, send: Sequence[int], recv: Sequence[int], group) -> torch.Tensor:
@@ -323,7 +346,8 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
                     to_host: bool = False, refine_step: int = 0, refine_snippet_len: int = 3,
                     refine_start_dilation: int = 6, gather: bool = False, record: Optional[dict] = None,
                     generator: Optional[torch.Generator] = None,
-                    init_infer_steps: Union[int, Sequence[int]] = 1, timing: Optional[list] = None) -> ShardedOutput:
+                    init_infer_steps: Union[int, Sequence[int]] = 1, timing: Optional[list] = None,
+                    strides: Union[int, Sequence[int]] = 1) -> ShardedOutput:
     """Multi-GPU RollingDepthPipeline.forward (every preset: refine_step > 0 included).
 
     `input_frames` is either the whole video [1,N,3,H,W] / [N,3,H,W], or — with `num_frames=N` —
@@ -336,9 +360,12 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     the world group (refine's all-reduce included).  `init_infer_steps`: DDIM steps per snippet, one
     count or one per dilation (rollingdepth_pipeline.py:421-445), as forward().  Without `init_noise` the shared noise is drawn
     on rank 0 exactly as forward() draws it (from `generator`) and broadcast.  `timing` (a list):
-    phase-boundary events (name, torch.cuda.Event) are appended to it (bench.py --slice-world)."""
+    phase-boundary events (name, torch.cuda.Event) are appended to it (bench.py --slice-world).
+    `strides`: frames between the starts of a dilation's consecutive snippets (forward()'s `strides`,
+    get_snippet_indice's `stride`; called start steps below), one int >= 1 or one per dilation; the
+    dilations' snippets together must reach every frame (ValueError before any inference, as forward())."""
     from . import kernels as K
-    from .aligner import DepthAligner, check_row_layout
+    from .aligner import DepthAligner, check_row_layout, snippet_count, snippet_last, snippet_start
 
     if group is None:
         group = dist.group.WORLD
@@ -362,6 +389,25 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
         refine_start_dilation = pipe.cap_max_dilation(N, refine_snippet_len, refine_start_dilation)
     if 1 not in dil:
         raise AssertionError("dilations should include 1")
+    start_steps = list(strides) if isinstance(strides, (list, tuple)) else [strides]
+    if len(start_steps) == 1:
+        start_steps = start_steps * len(dil)
+    if len(start_steps) != len(dil) or any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 1
+                                           for s in start_steps):
+        raise ValueError(f"strides must be ints >= 1, one or one per dilation ({len(dil)}), got {strides}")
+    start_steps = [int(s) for s in start_steps]
+    strided = _strided(start_steps)
+    if strided:  # forward()'s check: a frame in no snippet has cover count 0 (the reference divides 0 / 0)
+        covered = set()
+        for d, sl, ss in zip(dil, slens, start_steps):
+            if snippet_last(N, sl, d) >= 0:
+                for k in range(snippet_count(N, sl, d, ss)):
+                    q = snippet_start(k, N, sl, d, ss)
+                    covered.update(range(q, q + (sl - 1) * d + 1, d))
+        missing = [f for f in range(N) if f not in covered]
+        if missing:
+            raise ValueError(f"strides {start_steps} with dilations {dil} leave frame {missing[0]} "
+                             f"({len(missing)} of {N} frames) in no snippet")
     f0, f1 = chunk_bounds(N, world)[rank]
     mine_frames = frames[f0:f1] if num_frames is None else frames
     if num_frames is not None and mine_frames.shape[0] != f1 - f0:
@@ -384,13 +430,12 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     noise = pipe._noise_nhwc(init_noise, h, w)
     _mark(timing, "encode")
     # 2. my snippets (compact: row r of dilation d is global snippet subsets[d][r])
-    counts = [len(pipe.get_snippet_indice(0, [0], N, sl, d, d, 1)) for d, sl in zip(dil, slens)]
+    counts = [snippet_count(N, sl, d, ss) for d, sl, ss in zip(dil, slens, start_steps)]
     subsets = rank_subsets(counts, world, rank)
     k0 = [s[0] if s else 0 for s in subsets]
     aligner = DepthAligner(device=dev, **(coalign_kwargs or {}))
     check_row_layout(slens, aligner.num_iterations)
-    rows = pipe.init_snippet_infer(rgb_latent, noise, dil, slens, steps, [1] * len(dil),
-                                   snippet_subset=subsets)
+    rows = pipe.init_snippet_infer(rgb_latent, noise, dil, slens, steps, start_steps, snippet_subset=subsets)
     H, W = rows[0].shape[-2:]
     d2h = torch.cuda.Stream(dev) if to_host else None
     snip_host = [pipe._to_host_async(r.to(pipe.dtype), d2h) if r.shape[0] else None for r in rows] if to_host else None
@@ -405,15 +450,16 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
         ((W - 2 * aligner.border + aligner.factor - 1) // aligner.factor)
     xs = gather_rows_by_dilation([p if p is not None else torch.empty((0, sl, P), dtype=F32, device=dev)
                                   for p, sl in zip(prepared, slens)], counts, world, group)
-    strides = list(dil)
-    seq_len = aligner.sequence_length(counts, slens[0], dil)
-    assert seq_len == N
+    frame_steps = list(dil)
+    if not strided:  # a strided snippet count does not determine the sequence length
+        assert aligner.sequence_length(counts, slens[0], dil) == N
     _mark(timing, "prepare")
-    scales, trans, hist, ws = aligner.optimize_prepared(xs, strides, N)
+    scales, trans, hist, ws = aligner.optimize_prepared(xs, frame_steps, N, start_steps if strided else None)
     rows_f32 = rows[0].dtype == F32
     _mark(timing, "aligner")
-    merged = _merge_windowed(rows, k0, counts, scales, trans, strides, slens, N, H * W, shift,
-                             1 if rows_f32 else (2 if pipe.merge_f32 else 0), group)
+    merged = _merge_windowed(rows, k0, counts, scales, trans, frame_steps, slens, N, H * W, shift,
+                             1 if rows_f32 else (2 if pipe.merge_f32 else 0), group,
+                             start_steps if strided else None)
     # merge_scaled_triplets returns the snippets' dtype (unless the pipeline merges in f32)
     d = (merged if (pipe.merge_f32 or rows_f32) else merged.to(pipe.dtype).float()).contiguous()
     mm_d = K.minmax(d) if d.numel() else torch.tensor([float("inf"), float("-inf")], device=dev)

@@ -8,6 +8,15 @@ variant, then `rounds` rounds of the three in turn.  Per variant: the snippet co
 frames/s, the run-to-run spread, the aligner time (device time of DepthAligner.run) and — as information
 only — the mean |Δ depth_pred| against the [1, 1] run of the same process (the quality cost of the knob
 on synthetic weights: no bound).  The time base is the [1, 1] run of the same interleave.
+
+    python tools/stride_ab.py --slice-world 8 [--rounds 2]
+
+times instead each rank's share of a W-rank step of the three variants on this one GPU, under
+shard.SliceGroup (shard.sharded_forward(strides=…): the rank's encode chunk, its snippets, the replicated
+aligner, its strided window sums and finish; every collective a local no-op — what bench.py --slice-world
+does for stride 1).  Per variant: every rank's median step and phases, the slowest rank, and the
+single-GPU step of the same variant.  A rank-slice prediction, not a scaling result: nothing ran on W
+GPUs and the collectives' time is left out.
 """
 import argparse
 import json
@@ -23,12 +32,65 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 VARIANTS = ([1, 1], [1, 5], [2, 5])
 
 
+def slice_world(a, pipe, frames, noise, coalign, one):
+    """--slice-world W: per variant, each rank's share of the W-rank step timed alone on this GPU."""
+    from rollingdepth_amd.shard import SliceGroup, chunk_bounds, rank_subsets, sharded_forward
+
+    Wd, N = a.slice_world, a.frames
+    rows = []
+    for v in VARIANTS:
+        one(v)  # warm-up, then the single-GPU step of this variant
+        single = statistics.median(one(v)[0] for _ in range(a.rounds))
+        ranks = []
+        for r in range(Wd):
+            lo, hi = chunk_bounds(N, Wd)[r]
+            fr = frames[0, lo:hi]
+            g = SliceGroup(r, Wd)
+
+            def step(timing=None):
+                return sharded_forward(pipe, fr, [1, 25], True, 3, coalign, init_noise=noise, num_frames=N,
+                                       to_host=True, group=g, timing=timing, strides=list(v))
+
+            so = step()
+            torch.cuda.synchronize()
+            walls, phases = [], {}
+            for _ in range(a.rounds):
+                tm = []
+                t0 = time.perf_counter()
+                step(tm)
+                torch.cuda.synchronize()
+                walls.append(time.perf_counter() - t0)
+                for (_, e0), (n1, e1) in zip(tm, tm[1:]):
+                    phases[n1] = phases.get(n1, 0.0) + e0.elapsed_time(e1) / a.rounds
+            ranks.append({"rank": r, "ms": round(statistics.median(walls) * 1e3, 1), "frames": hi - lo,
+                          "snippets": [len(x) for x in rank_subsets(so.snippet_counts, Wd, r)],
+                          "phases_ms": {k: round(x, 1) for k, x in phases.items()}})
+            print(f"strides {v} W={Wd} rank {r}: {ranks[-1]['ms']} ms, snippets {ranks[-1]['snippets']}, "
+                  f"{ranks[-1]['phases_ms']}", flush=True)
+        slow = max(ranks, key=lambda x: x["ms"])
+        rows.append({"strides": v, "snippets": so.snippet_counts, "single_gpu_ms": round(single * 1e3, 1),
+                     "slowest_rank": slow["rank"], "slowest_rank_ms": slow["ms"],
+                     "fastest_rank_ms": min(x["ms"] for x in ranks), "ranks": ranks})
+    print(f"| strides | snippets | single GPU ms | slowest of {Wd} rank slices ms | its phases ms |")
+    print("|---|---|---|---|---|")
+    for row in rows:
+        ph = row["ranks"][row["slowest_rank"]]["phases_ms"]
+        print(f"| {row['strides']} | {' + '.join(map(str, row['snippets']))} | {row['single_gpu_ms']:.1f} | "
+              f"{row['slowest_rank_ms']:.1f} (rank {row['slowest_rank']}) | "
+              f"{', '.join(f'{k} {x:.1f}' for k, x in ph.items())} |")
+    print(json.dumps({"tool": "stride_ab", "mode": "rank-slice", "note": "each rank's share of a W-rank step timed "
+                      "alone on one GPU, collectives left out: a prediction, not a scaling result",
+                      "world": Wd, "frames": N, "res": a.res, "rounds": a.rounds, "rows": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--res", type=int, default=768)
     ap.add_argument("--aligner-iters", type=int, default=2000)
+    ap.add_argument("--slice-world", type=int, default=0,
+                    help="W: time each rank's share of a strided W-rank step on this GPU (shard.SliceGroup)")
     a = ap.parse_args()
 
     from rollingdepth_amd import aligner as A
@@ -65,6 +127,9 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         return dt, events[0][0].elapsed_time(events[0][1]), out
+
+    if a.slice_world:
+        return slice_world(a, pipe, frames, noise, coalign, one)
 
     res = {tuple(v): {"s": [], "aligner_ms": []} for v in VARIANTS}
     for v in VARIANTS:  # warm-up (and the outputs: every run of a variant computes the same values)
