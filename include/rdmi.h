@@ -308,9 +308,9 @@ int rdmi_renormalize_f32(float* x, long n, const float* minmax, void* stream);
  * With every start step 1 the calls run the kernels of version 1 unchanged.  Only when some start step
  * is > 1 is the layout checked, before any launch: a negative start step, seq_len < win or an n_d other
  * than the count above → RDMI_E_ARG with a rdmi_last_error text.  The loss still means over the full
- * [Σw, seq_len, P] tensor.  Such a job runs the three- or the two-launch loop: under
- * RDMI_ALIGNER_FUSED=2 (the opt-in persistent loop) it takes the two-launch loop, and
- * rdmi_aligner_workspace sizes the workspace for the loop that will run.  The sharded merge calls
+ * [Σw, seq_len, P] tensor.  rdmi_aligner_workspace depends only on the arguments (seq_len, P, Σ n_d,
+ * iters, history or not — csrc/aligner_ws.h), never on the environment or the start steps: a workspace
+ * sized once serves every later call with the same arguments.  The sharded merge calls
  * (partial_window / finish_pieces) keep start step 1; since rdmi_version 3 their _strided forms take the
  * start steps, with the same check before any launch.
  */

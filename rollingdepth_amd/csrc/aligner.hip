@@ -30,22 +30,19 @@
 // outside the pixel loops).  The kernels that derive frames are templated on SS; the SS = false
 // instantiations are the start-step-1 kernels with their launch geometry and float operation order,
 // and a job whose start steps are all 1 runs only those.  The loss denominator stays Σw · N · P.
-// The persistent loop is start-step-1 only; the sharded merge takes start steps through its _strided
-// entry points (window sums: merge_k<true>; cover count: rdmi_cover_count).
+// The sharded merge takes start steps through its _strided entry points (window sums: merge_k<true>;
+// cover count: rdmi_cover_count).
 #pragma clang fp contract(off)
-#include <type_traits>
-
 #include "common.h"
 #include "aligner_index.h"
+#include "aligner_ws.h"
 
 namespace {
 
 constexpr int MAXD = 8;
 constexpr int MAXR = 64;  // rows Σ w_d of the reference's M / M_depth / B tensors
-// Pixel chunks per frame / per snippet: frame_stats and snippet_grad run N·PS and ntot·PS
-// workgroups (one workgroup per frame or snippet alone left most of the 256 CUs idle and each
-// latency-bound), partial sums combined in a fixed chunk order by the consumer (deterministic).
-constexpr int PS = 8;
+constexpr int PS = RDMI_ALIGNER_PS;      // pixel chunks per frame / per snippet (aligner_ws.h)
+constexpr int HBLK = RDMI_ALIGNER_HBLK;  // iterations per block of history slots (aligner_ws.h)
 
 struct AlP {
   const float* x[MAXD];
@@ -485,426 +482,6 @@ __global__ __launch_bounds__(256) void aligner_history(AlP p, double denom, cons
   });
 }
 
-// ---------------------------------------------------------------------------------------------
-// Persistent single-launch loop (opt-in, RDMI_ALIGNER_FUSED=2, where aligner_persist_upt fits).  The two-launch
-// iteration spends ≈26 µs per iteration on two dependent kernels whose work is a few µs: each
-// re-reads the snippets and the per-frame means from beyond the L2 and writes them back.  Here ONE
-// workgroup per frame f runs all iterations: it loads the covering slots' subsampled pixels of f
-// into registers once, and per iteration computes the means T, Td of f (frame_stats), the frame's
-// L1 scales, and each covering slot's gradient partials Σ_px g·x, Σ_px g (snippet_grad) — all
-// frame-local, because every term of a slot's gradient lives on that slot's frame.  The partials
-// (2 doubles per (snippet, slot)) are published as agent-scope atomic stores, one grid barrier
-// (arrival counter, bounded spin: a grid that is not co-resident fails with an error instead of
-// hanging), then EVERY workgroup applies Adam to every parameter from the same partials in the same
-// order — identical copies of s, t, m, v in each workgroup's LDS, no second exchange.  Per pixel the
-// arithmetic is frame_stats / snippet_grad's, in the same f32 op order; the f64 sums group the same
-// terms differently (per slot, then slots in order, instead of per pixel chunk), which changes an
-// f64 sum by ~1e-16 relative — below the f32 rounding of the gradient except with probability
-// ~1e-9 per value (tests/test_aligner_gpu.py::test_aligner_fused_loop_bitwise checks the results bitwise
-// against the two- and three-launch loops).  Measured (tools/aligner_ab.py, STAMP build): with one
-// workgroup per frame and 64-lane butterflies for the block sums, 56 vs 52 ms per 2 000 iterations — the
-// 14-double gradient sum alone was ≈20k cycles of cross-lane shuffles; with two workgroups per frame (each
-// the frame's means over all pixels, the gradient over half the pixel rounds) and the reduce-scatter sum
-// (psums16), 48.9 vs 52.4 ms.  Opt-in: the whole aligner is ≈1 % of a fast-preset step.
-constexpr int PT = 1024;      // threads per workgroup (one workgroup per frame)
-constexpr int PCM = 6;        // covering slots per frame held in registers (the fast preset: 3 + 3)
-constexpr int PMAXS = 1024;   // snippets (ntot) whose s, t, m, v live in LDS
-
-struct PerP {
-  int iters;
-  int wmax;                   // max snippet length (partial slots per snippet)
-  double denom;
-  long spin_limit;
-  double* part;               // [2][ntot][wmax][2] gradient partials (Σ g·x, Σ g), by iteration parity
-  unsigned* bar;              // [0] arrival counter, [1] error flag
-  double* hl;                 // [iters][N][2] per-frame loss partials (history), or NULL
-  float* hmm;                 // [iters][N][2] per-frame min / max of T (history)
-  float* hst;                 // [iters][2 ntot] parameters before each update (history)
-};
-
-// Sums of NV doubles over the 1024-thread block (xor butterfly per wave, then the 16 wave partials
-// in wave order); every thread gets the results.
-template <int NV>
-__device__ __forceinline__ void psums(double (&v)[NV], double* sh /* [16 * NV + NV] */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] += __shfl_xor(v[i], o, 64);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int i = 0; i < NV; ++i) sh[w * NV + i] = v[i];
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double r = 0.0;
-    for (int k = 0; k < PT / 64; ++k) r += sh[k * NV + threadIdx.x];
-    sh[(PT / 64) * NV + threadIdx.x] = r;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = sh[(PT / 64) * NV + i];
-  __syncthreads();  // sh reusable
-}
-
-// Sums of 16 doubles over the 1024-thread block with a reduce-scatter butterfly: at lane offsets 32, 16, 8, 4
-// each lane keeps half of its values and adds the partner's copy of that half (8 + 4 + 2 + 1 shuffles instead of
-// 4 × 16), so lane 4i ends with value i's wave sum after two more levels; then the 16 wave sums in wave order.
-// Every thread gets the results.  (A fixed order: deterministic; the grouping differs from psums.)
-__device__ __forceinline__ void psums16(double (&v)[16], double* sh /* [16 * 16 + 16] */) {
-  const int lane = threadIdx.x & 63;
-  double a8[8], a4[4], a2[2], a1;
-  const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8, b2 = lane & 4;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a8[i] = (b5 ? v[i + 8] : v[i]) + __shfl_xor(b5 ? v[i] : v[i + 8], 32, 64);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) a4[i] = (b4 ? a8[i + 4] : a8[i]) + __shfl_xor(b4 ? a8[i] : a8[i + 4], 16, 64);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) a2[i] = (b3 ? a4[i + 2] : a4[i]) + __shfl_xor(b3 ? a4[i] : a4[i + 2], 8, 64);
-  a1 = (b2 ? a2[1] : a2[0]) + __shfl_xor(b2 ? a2[0] : a2[1], 4, 64);
-  a1 += __shfl_xor(a1, 2, 64);
-  a1 += __shfl_xor(a1, 1, 64);
-  const int w = threadIdx.x >> 6;
-  if ((lane & 3) == 0) sh[w * 16 + (lane >> 2)] = a1;
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double r = 0.0;
-    for (int k = 0; k < PT / 64; ++k) r += sh[k * 16 + threadIdx.x];
-    sh[(PT / 64) * 16 + threadIdx.x] = r;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v[i] = sh[(PT / 64) * 16 + i];
-  __syncthreads();  // sh reusable
-}
-
-// Grid barrier of iteration `it` (all N workgroups arrive once per iteration on one monotonic counter).
-// Thread 0's agent-scope partial stores are complete (vmcnt) before it arrives, as in snippet_grad_adam.
-__device__ __forceinline__ bool pbarrier(const PerP& q, unsigned target) {
-  __shared__ int ok;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_fetch_add(q.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int good = 1;
-    long n = 0;
-    while (__hip_atomic_load(q.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      if ((++n & 1023) == 0 &&
-          (n > q.spin_limit || __hip_atomic_load(q.bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-        __hip_atomic_store(q.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        good = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    ok = good;
-  }
-  __syncthreads();
-  return ok != 0;
-}
-
-__device__ __forceinline__ unsigned long long al_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
-// STAMP = 1 (diagnostic, RDMI_ALIGNER_STAMPS=1): workgroup 0 prints its cycle sums per segment.
-// snippet_grad's per-(pixel, slot) terms over the pixel rounds [U0, U1) of the persistent loop
-template <int U0, int U1, int UPT>
-__device__ __forceinline__ void persist_grad(const AlP& p, const float (&xv)[PCM][UPT], const float (&T)[UPT],
-                                             const float (&Td)[UPT], const float* se, const float* te, int cnt,
-                                             float isc, float iscd, long P, int tid, double (&g)[16]) {
-#pragma unroll
-  for (int e = 0; e < PCM; ++e) {
-    if (e < cnt) {
-#pragma unroll
-      for (int u = U0; u < U1; ++u) {
-        if (tid + (long)u * PT < P) {
-          const float xvv = xv[e][u];
-          float a = addrn(mulrn(xvv, se[e]), te[e]);
-          float z = a - T[u];
-          float ac = fmaxf(a, 1e-3f);
-          float ad = 1.0f / ac;
-          float zd = ad - Td[u];
-          float g1 = (z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f)) * isc;
-          float g2 = 0.f;
-          if (a >= 1e-3f) g2 = (zd > 0.f ? 1.f : (zd < 0.f ? -1.f : 0.f)) * iscd * (-1.0f / (ac * ac));
-          double gg = (double)g1 + (double)p.dw * (double)g2;
-          g[2 * e] += gg * (double)xvv;
-          g[2 * e + 1] += gg;
-          g[2 * PCM] += fabs((double)z) * (double)isc;
-          g[2 * PCM + 1] += fabs((double)zd) * (double)iscd;
-        }
-      }
-    }
-  }
-}
-
-// H workgroups per frame (blockIdx.y = hh): each computes the frame's means and scales over all its
-// pixels (cheap) and the gradient partials of its 1/H of the pixel rounds (the costly part).
-template <int UPT, int H, int STAMP = 0>
-__global__ __launch_bounds__(PT, 1) void aligner_persist_k(AlP p, PerP q) {
-  const int f = blockIdx.x, hh = blockIdx.y, tid = threadIdx.x;
-  static_assert(UPT % H == 0, "pixel rounds split evenly");
-  unsigned long long st[5] = {}, tp = 0;
-  auto seg = [&](int i) __attribute__((always_inline)) {
-    if constexpr (STAMP) {
-      const unsigned long long t = al_stamp();
-      if (i >= 0) st[i] += t - tp;
-      tp = t;
-    }
-  };
-  const int ntot = p.ntot, np = 2 * ntot;
-  __shared__ float prm[2 * PMAXS], am[2 * PMAXS], av[2 * PMAXS];
-  __shared__ int egk[PCM], ej[PCM], ecnt;
-  __shared__ const float* ex[PCM];
-  __shared__ double sh[(PT / 64 + 1) * 16];
-  __shared__ float rmm[2][PT / 64];
-  // parameters (global snippet order: s then t), Adam moments zero (torch.optim.Adam's initial state)
-  for (int i = tid; i < np; i += PT) {
-    const int gk = i < ntot ? i : i - ntot;
-    int d = 0;
-    while (d + 1 < p.nd && gk >= p.off[d + 1]) ++d;
-    prm[i] = i < ntot ? p.s[d][gk - p.off[d]] : p.t[d][gk - p.off[d]];
-    am[i] = 0.f;
-    av[i] = 0.f;
-  }
-  // the slots covering frame f in row order (frame_stats_body's compaction)
-  if (tid < 64) {
-    const int r = tid;
-    int k = 0;
-    const int d = r < p.R ? row_owner<false>(p, r, f, k) : -1;
-    const unsigned long long m = __ballot(d >= 0);
-    const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-    if (d >= 0 && slot < PCM) {
-      ex[slot] = p.x[d] + ((long)k * p.w[d] + (r - p.rb[d])) * p.P;
-      egk[slot] = p.off[d] + k;
-      ej[slot] = r - p.rb[d];
-    }
-    if (r == 0) ecnt = __popcll(m);
-  }
-  __syncthreads();
-  const int cnt = ecnt;
-  if (cnt > PCM) {  // the host checks this (aligner_persist_upt); never half-run
-    if (tid == 0) __hip_atomic_store(q.bar + 1, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  const long P = p.P;
-  float xv[PCM][UPT];
-#pragma unroll
-  for (int e = 0; e < PCM; ++e)
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const long px = tid + (long)u * PT;
-      xv[e][u] = (e < cnt && px < P) ? ex[e][px] : 0.f;
-    }
-  const float gscale = (float)(p.ls / q.denom);
-  const float lw = 1.0f - p.b1, vw = 1.0f - p.b2;
-  seg(-1);
-  for (int it = 1; it <= q.iters; ++it) {
-    const int buf = it & 1;
-    // this iteration's s, t of the covering slots (LDS, read where used: registers are the limit)
-    __shared__ float se[PCM], te[PCM];
-    if (tid < cnt) {
-      se[tid] = prm[egk[tid]];
-      te[tid] = prm[ntot + egk[tid]];
-    }
-    __syncthreads();
-    // ---- frame_stats: T, Td per pixel (slots in row order), Σ|T|, Σ|Td|, min / max T
-    float T[UPT], Td[UPT];
-    double v2[2] = {0.0, 0.0};
-    float mn = INFINITY, mx = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      float sum = 0.f, sumd = 0.f;
-#pragma unroll
-      for (int e = 0; e < PCM; ++e) {
-        if (e < cnt) {
-          float a = addrn(mulrn(xv[e][u], se[e]), te[e]);
-          float ac = fmaxf(a, 1e-3f);
-          sum = addrn(sum, a);
-          sumd = addrn(sumd, 1.0f / ac);
-        }
-      }
-      T[u] = Td[u] = 0.f;
-      if (cnt) {
-        T[u] = sum / (float)cnt;
-        Td[u] = sumd / (float)cnt;
-      }
-      if (tid + (long)u * PT < P) {
-        v2[0] += fabs((double)T[u]);
-        v2[1] += fabs((double)Td[u]);
-        mn = fminf(mn, T[u]);
-        mx = fmaxf(mx, T[u]);
-      }
-    }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) {
-      rmm[0][tid >> 6] = mn;
-      rmm[1][tid >> 6] = mx;
-    }
-    psums<2>(v2, sh);  // its barriers also publish rmm
-    seg(0);
-    const float scf = (float)(v2[0] / (double)P), scdf = (float)(v2[1] / (double)P);
-    const float isc = 1.0f / scf, iscd = 1.0f / scdf;
-    // ---- snippet_grad: per covering slot Σ g·x, Σ g; the frame's loss partials
-    double g[16];  // 2 per covering slot, the two loss partials at 2·PCM, 2·PCM + 1 (PCM ≤ 7), padding
-    static_assert(2 * PCM + 2 <= 16, "psums16 holds 16 values");
-#pragma unroll
-    for (int i = 0; i < 16; ++i) g[i] = 0.0;
-    // the pixel rounds [U0, U1) of this workgroup: a uniform branch between compile-time ranges (a per-round
-    // predicate was if-converted by the compiler, every workgroup then computing every round)
-    if (H == 1)
-      persist_grad<0, UPT>(p, xv, T, Td, se, te, cnt, isc, iscd, P, tid, g);
-    else if (hh == 0)
-      persist_grad<0, UPT / H>(p, xv, T, Td, se, te, cnt, isc, iscd, P, tid, g);
-    else
-      persist_grad<UPT / H, UPT>(p, xv, T, Td, se, te, cnt, isc, iscd, P, tid, g);
-    psums16(g, sh);
-    seg(1);
-    if (tid == 0) {
-      double* pb = q.part + (long)buf * ntot * q.wmax * H * 2;
-      for (int e = 0; e < cnt; ++e) {
-        double* o = pb + (((long)egk[e] * q.wmax + ej[e]) * H + hh) * 2;
-        __hip_atomic_store(o, g[2 * e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(o + 1, g[2 * e + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (q.hl) {
-        const long h = (long)(it - 1) * p.N + f;
-        q.hl[2 * (h * H + hh)] = g[2 * PCM];
-        q.hl[2 * (h * H + hh) + 1] = g[2 * PCM + 1];
-        float lo = rmm[0][0], hi = rmm[1][0];
-        for (int w = 1; w < PT / 64; ++w) {
-          lo = fminf(lo, rmm[0][w]);
-          hi = fmaxf(hi, rmm[1][w]);
-        }
-        q.hmm[2 * h] = lo;
-        q.hmm[2 * h + 1] = hi;
-      }
-    }
-    seg(2);
-    if (!pbarrier(q, (unsigned)it * gridDim.x * gridDim.y)) {  // not co-resident / timed out: fail loudly (NaN s, t)
-      if (f == 0 && hh == 0)
-        for (int i = tid; i < np; i += PT) {
-          const int gk = i < ntot ? i : i - ntot;
-          int d = 0;
-          while (d + 1 < p.nd && gk >= p.off[d + 1]) ++d;
-          (i < ntot ? p.s[d] : p.t[d])[gk - p.off[d]] = __builtin_nanf("");
-        }
-      return;
-    }
-    // ---- Adam on every parameter (adam_param's f32 op order), the same in every workgroup
-    seg(3);
-    const double bc1 = p.bct[2 * it], bc2 = p.bct[2 * it + 1];
-    const float step_size = (float)(p.lr / bc1);
-    const float bc2s = (float)sqrt(bc2);
-    const double* pb = q.part + (long)buf * ntot * q.wmax * H * 2;
-    for (int i = tid; i < np; i += PT) {
-      const bool is_t = i >= ntot;
-      const int gk = is_t ? i - ntot : i;
-      int d = 0;
-      while (d + 1 < p.nd && gk >= p.off[d + 1]) ++d;
-      const int k = gk - p.off[d];
-      double gsum = 0.0;
-      for (int j = 0; j < p.w[d]; ++j) {
-        int kk = 0;
-        if (row_owner<false>(p, p.rb[d] + j, k + j * p.stride[d], kk) != d) continue;  // overwritten slot: no term
-#pragma unroll
-        for (int h2 = 0; h2 < H; ++h2)
-          gsum += __hip_atomic_load(pb + (((long)gk * q.wmax + j) * H + h2) * 2 + (is_t ? 1 : 0), __ATOMIC_RELAXED,
-                                    __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const float pv = prm[i];
-      float gf = (float)(gsum * (double)gscale);
-      const float nd = (float)p.n[d];
-      if (!is_t) {
-        float r = fmaxf(0.f, 1.f - pv);
-        gf = addrn(gf, mulrn(mulrn(mulrn(p.lmda2, 2.0f), r), -1.0f) / nd);
-      } else {
-        gf = addrn(gf, mulrn(mulrn(p.lmda3, 2.0f), pv) / nd);
-      }
-      float m = am[i], v = av[i];
-      const float diff = gf - m;
-      m = (lw < 0.5f) ? addrn(m, mulrn(lw, diff)) : gf - mulrn(diff, 1.0f - lw);
-      v = addrn(mulrn(v, p.b2), mulrn(mulrn(vw, gf), gf));
-      const float den = addrn(sqrtf(v) / bc2s, p.eps);
-      prm[i] = addrn(pv, mulrn(-step_size, m) / den);
-      am[i] = m;
-      av[i] = v;
-      if (q.hst && f == 0 && hh == 0) q.hst[(long)(it - 1) * np + i] = pv;
-    }
-    __syncthreads();
-    seg(4);
-  }
-  if constexpr (STAMP) {
-    if ((f == 0 || f == gridDim.x / 2) && hh == 0 && tid == 0)
-      printf("aligner_persist wg %d cycles per iteration: stats %.0f grad %.0f publish %.0f barrier %.0f adam %.0f\n", f,
-             (double)st[0] / q.iters, (double)st[1] / q.iters, (double)st[2] / q.iters, (double)st[3] / q.iters,
-             (double)st[4] / q.iters);
-  }
-  if (f == 0 && hh == 0)
-    for (int i = tid; i < np; i += PT) {
-      const int gk = i < ntot ? i : i - ntot;
-      int d = 0;
-      while (d + 1 < p.nd && gk >= p.off[d + 1]) ++d;
-      (i < ntot ? p.s[d] : p.t[d])[gk - p.off[d]] = prm[i];
-    }
-}
-
-// History rows of the persistent loop: iteration it0 + blockIdx.x from its per-frame partials (hist_row
-// with the loss summed over frames instead of over (snippet, pixel chunk) partials)
-__global__ __launch_bounds__(256) void aligner_history_frames(AlP p, double denom, const double* hl, const float* hmm,
-                                                              const float* hst, int H) {
-  const int it = 1 + blockIdx.x;
-  const long h0 = (long)(it - 1) * p.N;
-  __shared__ double sh[8];
-  double L1 = 0.0, L2 = 0.0, soft = 0.0;
-  for (int i = threadIdx.x; i < p.N * H; i += 256) {
-    L1 += hl[2 * (h0 * H + i)];
-    L2 += hl[2 * (h0 * H + i) + 1];
-  }
-  L1 = block_sum_d<256>(L1, sh);
-  L2 = block_sum_d<256>(L2, sh);
-  const float* sflat = hst + (long)(it - 1) * 2 * p.ntot;
-  for (int d = 0; d < p.nd; ++d) {
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < p.n[d]; k += 256) {
-      const float sv = sflat[p.off[d] + k];
-      const float tv = sflat[p.ntot + p.off[d] + k];
-      float r = fmaxf(0.f, 1.f - sv);
-      a += (double)r * r;
-      b += (double)tv * tv;
-    }
-    a = block_sum_d<256>(a, sh);
-    b = block_sum_d<256>(b, sh);
-    soft += p.lmda2 * a / p.n[d] + p.lmda3 * b / p.n[d];
-  }
-  float mn = INFINITY, mx = -INFINITY;
-  for (int i = threadIdx.x; i < p.N; i += 256) {
-    mn = fminf(mn, hmm[2 * (h0 + i)]);
-    mx = fmaxf(mx, hmm[2 * (h0 + i) + 1]);
-  }
-  mn = wave_min(mn);
-  mx = wave_max(mx);
-  __shared__ float r2[2][4];
-  if ((threadIdx.x & 63) == 0) {
-    r2[0][threadIdx.x >> 6] = mn;
-    r2[1][threadIdx.x >> 6] = mx;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    mn = fminf(fminf(r2[0][0], r2[0][1]), fminf(r2[0][2], r2[0][3]));
-    mx = fmaxf(fmaxf(r2[1][0], r2[1][1]), fmaxf(r2[1][2], r2[1][3]));
-    float* h = p.hist + 3L * (it - 1);
-    h[0] = (float)(p.ls * (L1 / denom + p.dw * L2 / denom) + soft);
-    h[1] = mn;
-    h[2] = mx;
-  }
-}
-
 // Adam's bias corrections of every step, once per optimisation (the same double pow the update
 // evaluated per parameter before: two double pows off each iteration's critical path)
 __global__ void adam_bc_k(AlP p, int iters, double* bct) {
@@ -1042,59 +619,11 @@ __global__ void prepare_k(PrepP p) {
   }
 }
 
-// Iterations per block of history slots: the fused loop keeps per-iteration loss partials for at
-// most HBLK iterations, so the workspace does not grow with the iteration count (1500 frames with
-// [1,10,25] at 2000 iterations would otherwise need 1.4 GB).
-constexpr int HBLK = 128;
-
-// RDMI_ALIGNER_FUSED (read per call: A/B and the bitwise tests): 0 the three-kernel loop, unset / 1 the
-// two-launch loop (default), 2 the persistent loop where aligner_persist_upt fits (opt-in: bitwise the
-// same results, 48.9 vs 52.4 ms per 2 000 iterations at the fast preset — DESIGN App. A)
+// RDMI_ALIGNER_FUSED (read per call: A/B and the bitwise tests): 0 the three-kernel loop, anything else
+// or unset the two-launch loop (default).  The workspace is the same for both (aligner_ws.h).
 int loop_mode() {
   const char* e = getenv("RDMI_ALIGNER_FUSED");
-  return e && (e[0] == '0' || e[0] == '2') ? e[0] - '0' : 1;
-}
-
-// Workspace (floats): 4 double arrays (ntot·PS each), fpart (N·PS·4 doubles), T, Td (N·P each), m, v
-// (2·ntot each), the per-snippet arrival counters (ntot, padded to 8 B), the bias-correction table
-// ((iters + 1)·2 doubles); with a history, the
-// fused loop's per-iteration slots for min(iters, HBLK) iterations: loss partials (2·ntot·PS
-// doubles), chunk min/max (2·N·PS) and pre-update parameters (2·ntot).
-long ws_floats(int N, long P, int ntot, int iters, bool hist, int wmax, bool strided) {
-  long f = 8L * ntot * PS + 8L * N * PS + 2L * N * P + 4L * ntot + ((ntot + 1) & ~1L) + 4L * (iters + 1);
-  // the persistent loop (opt-in, loop_mode 2): partials (2 parities), barrier words, per-iteration history
-  // (a job with a start step > 1 takes the two-launch loop under loop_mode 2: nothing reserved)
-  if (loop_mode() == 2 && !strided)
-    f += 16L * ntot * wmax + 2 + (hist ? 10L * iters * N + 2L * iters * ntot : 0);  // H <= 2
-  const long slots = iters < HBLK ? iters : HBLK;
-  if (hist) f += slots * (4L * ntot * PS + 2L * N * PS + 2L * ntot) + 2;
-  return f + 64;
-}
-
-
-// pixels per thread of the persistent loop (0: it does not fit).  Its grid is one workgroup per frame,
-// all resident at once (one per CU at most is needed), ≤ PCM covering slots per frame, ≤ PMAXS snippets.
-int aligner_persist_upt(const AlP& p, int iters) {
-  if (iters < 1 || p.ntot > PMAXS || p.P > 6L * PT) return 0;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || p.N > cus)
-    return 0;
-  for (int f = 0; f < p.N; ++f) {  // covering slots of frame f (row_owner on the host)
-    int c = 0;
-    for (int r = 0; r < p.R; ++r)
-      for (int d = p.nd - 1; d >= 0; --d) {
-        const int j = r - p.rb[d];
-        if (j < 0 || j >= p.w[d]) continue;
-        const int k = f - j * p.stride[d];
-        if (k < 0 || k >= p.n[d]) continue;
-        ++c;
-        break;
-      }
-    if (c > PCM) return 0;
-  }
-  const long u = (p.P + PT - 1) / PT;
-  return u <= 2 ? 2 : u <= 4 ? 4 : 6;  // 6: 123 VGPRs at 16 waves per CU, no spill (8 spills)
+  return e && e[0] == '0' ? 0 : 1;
 }
 
 bool any_start_step(int nd, const int* start_step) {
@@ -1131,10 +660,7 @@ int start_steps(const char* what, int nd, const int* start_step, const int* n, c
 extern "C" long rdmi_aligner_workspace(const rdmi_aligner_args* a) {
   int ntot = 0;
   for (int d = 0; d < a->n_dil; ++d) ntot += a->n[d];
-  int wmax = 1;
-  for (int d = 0; d < a->n_dil; ++d) wmax = a->w[d] > wmax ? a->w[d] : wmax;
-  return ws_floats(a->seq_len, a->P, ntot, a->iters, a->history != nullptr, wmax,
-                   any_start_step(a->n_dil, a->start_step));
+  return rdmi_aligner_ws_layout(a->seq_len, a->P, ntot, a->iters, a->history != nullptr).total;
 }
 
 extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
@@ -1174,88 +700,26 @@ extern "C" int rdmi_aligner_optimize(const rdmi_aligner_args* a, void* stream) {
   p.lmda2 = a->lmda2; p.lmda3 = a->lmda3; p.dw = a->depth_w; p.ls = a->loss_scale;
   float* w = a->workspace;
   RDMI_REQUIRE(((uintptr_t)w & 7) == 0, RDMI_E_ALIGN, "aligner: workspace must be 8-byte aligned");
-  double* dw = (double*)w;
-  const long nps = (long)ntot * PS;
-  p.gs = dw; p.gt = dw + nps; p.l1 = dw + 2 * nps; p.l2 = dw + 3 * nps;
-  p.fpart = dw + 4 * nps;
-  float* fw = (float*)(p.fpart + 4L * p.N * PS);
-  p.T = fw; fw += (long)p.N * p.P;
-  p.Td = fw; fw += (long)p.N * p.P;
-  p.m = fw; fw += 2 * ntot;
-  p.v = fw; fw += 2 * ntot;
-  unsigned* cnt = (unsigned*)fw; fw += (ntot + 1) & ~1L;
-  double* bct = (double*)fw; fw += 4L * (a->iters + 1);
-  p.bct = bct;
   p.hist = a->history;
+  const rdmi_aligner_layout L = rdmi_aligner_ws_layout(p.N, p.P, ntot, a->iters, p.hist != nullptr);
+  p.gs = (double*)(w + L.gs); p.gt = (double*)(w + L.gt); p.l1 = (double*)(w + L.l1); p.l2 = (double*)(w + L.l2);
+  p.fpart = (double*)(w + L.fpart);
+  p.T = w + L.T;
+  p.Td = w + L.Td;
+  p.m = w + L.m;
+  p.v = w + L.v;
+  unsigned* cnt = (unsigned*)(w + L.cnt);
+  double* bct = (double*)(w + L.bct);
+  p.bct = bct;
   const double denom = (double)p.R * p.N * (double)p.P;  // numel of the [Σw, N, P] loss tensor
-  hipLaunchKernelGGL(zero_f32, dim3(16), dim3(256), 0, st, p.m, 4L * ntot + ((ntot + 1) & ~1L));  // m, v, cnt
+  hipLaunchKernelGGL(zero_f32, dim3(16), dim3(256), 0, st, p.m, L.bct - L.m);  // m, v, cnt: contiguous
   hipLaunchKernelGGL(adam_bc_k, dim3(8), dim3(256), 0, st, p, a->iters, bct);
   int rc = rdmi::check_launch("aligner_zero");
   if (rc) return rc;
-  int wmax = 1;
-  for (int d = 0; d < p.nd; ++d) wmax = p.w[d] > wmax ? p.w[d] : wmax;
-  // a job with a start step > 1 takes the two-launch loop where the persistent one was asked for
-  const int mode = loop_mode() == 2 && strided ? 1 : loop_mode();
-  PerP q{};
-  q.iters = a->iters;
-  q.wmax = wmax;
-  q.denom = denom;
-  q.spin_limit = 1L << 22;
-  if (mode == 2) {  // the region ws_floats reserves for mode 2 only
-    q.part = (double*)fw; fw += 16L * ntot * wmax;
-    q.bar = (unsigned*)fw; fw += 2;
-    if (p.hist) {
-      q.hl = (double*)fw; fw += 8L * a->iters * p.N;
-      q.hmm = fw; fw += 2L * a->iters * p.N;
-      q.hst = fw; fw += 2L * a->iters * ntot;
-    }
-  }
-  const int upt = mode == 2 ? aligner_persist_upt(p, a->iters) : 0;
-  if (upt) {
-    hipLaunchKernelGGL(zero_f32, dim3(1), dim3(64), 0, st, (float*)q.bar, 2L);  // arrival counter, error flag
-    int cus = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int H = (upt % 2 == 0 && 2 * p.N <= cus && !getenv("RDMI_ALIGNER_PERSIST_H1")) ? 2 : 1;
-    const dim3 g(p.N, H);
-    const bool stamps = getenv("RDMI_ALIGNER_STAMPS") != nullptr;
-    if (H == 2) {
-      if (upt == 2)
-        hipLaunchKernelGGL((aligner_persist_k<2, 2>), g, dim3(PT), 0, st, p, q);
-      else if (upt == 4)
-        hipLaunchKernelGGL((aligner_persist_k<4, 2>), g, dim3(PT), 0, st, p, q);
-      else if (stamps)
-        hipLaunchKernelGGL((aligner_persist_k<6, 2, 1>), g, dim3(PT), 0, st, p, q);
-      else
-        hipLaunchKernelGGL((aligner_persist_k<6, 2>), g, dim3(PT), 0, st, p, q);
-    } else {
-      if (upt == 2)
-        hipLaunchKernelGGL((aligner_persist_k<2, 1>), g, dim3(PT), 0, st, p, q);
-      else if (upt == 4)
-        hipLaunchKernelGGL((aligner_persist_k<4, 1>), g, dim3(PT), 0, st, p, q);
-      else if (stamps)
-        hipLaunchKernelGGL((aligner_persist_k<6, 1, 1>), g, dim3(PT), 0, st, p, q);
-      else
-        hipLaunchKernelGGL((aligner_persist_k<6, 1>), g, dim3(PT), 0, st, p, q);
-    }
-    rc = rdmi::check_launch("aligner_persist");
-    if (rc) return rc;
-    if (p.hist) {
-      hipLaunchKernelGGL(aligner_history_frames, dim3(a->iters), dim3(256), 0, st, p, denom, (const double*)q.hl,
-                         (const float*)q.hmm, (const float*)q.hst, H);
-      return rdmi::check_launch("aligner_history");
-    }
-    return 0;
-  }
-  if (mode != 0) {
-    double* hl = nullptr;
-    float *hmm = nullptr, *hst = nullptr;
-    const long slots = a->iters < HBLK ? a->iters : HBLK;
-    if (p.hist) {
-      hl = (double*)fw;
-      hmm = (float*)(hl + slots * 2 * nps);
-      hst = hmm + slots * 2 * p.N * PS;
-    }
+  if (loop_mode() != 0) {
+    double* hl = p.hist ? (double*)(w + L.hl) : nullptr;
+    float* hmm = p.hist ? w + L.hmm : nullptr;
+    float* hst = p.hist ? w + L.hst : nullptr;
     int it0 = 1;  // first iteration whose history slots are not yet turned into rows
     for (int it = 1; it <= a->iters; ++it) {
       const long slot = (it - 1) % HBLK;

@@ -104,6 +104,25 @@ def test_aligner_index_header_under_sanitizers(tmp_path):
     assert " 0 failures" in r.stdout and "6672 cases" in r.stdout, r.stdout
 
 
+def test_aligner_workspace_layout_under_sanitizers(tmp_path):
+    """csrc/aligner_ws.h (the workspace layout rdmi_aligner_workspace and rdmi_aligner_optimize share) in
+    a stand-alone program built with AddressSanitizer + UBSan, sanitizer runtimes linked statically: for
+    N ≤ 40, P in {1, 9, 5929}, ntot in {1, 2, 12, 148, 1024}, iters in {0, 1, 20, 128, 129, 2000}, with
+    and without a history, every region lies inside the total, the regions are disjoint and in the
+    documented order, f64 regions start at even float offsets, m / v / counters are contiguous and the
+    total is the closed formula."""
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build tests/cpp/aligner_ws_check.cpp"
+    exe = str(tmp_path / "aligner_ws_check")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
+                    "-I", os.path.join(ROOT, "rollingdepth_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "aligner_ws_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 failures" in r.stdout and "7200 cases" in r.stdout, r.stdout
+
+
 def _args(n, start_step, N=14, stride=(1, 3), w=(3, 3), P=9):
     """Aligner arguments with host buffers behind every pointer (never read: the calls below are
     rejected before any launch)."""
@@ -153,12 +172,12 @@ def test_start_step_validation_without_gpu():
 
 def test_start_step_workspace(monkeypatch):
     """A zero-initialised start_step (callers built against version 1) and explicit ones leave
-    rdmi_aligner_workspace at its value; under RDMI_ALIGNER_FUSED=2 a job with a start step > 1 is sized
-    for the two-launch loop it will take, not for the persistent one."""
+    rdmi_aligner_workspace at its value, and the size depends on the arguments alone: the same with
+    RDMI_ALIGNER_FUSED unset, 0, 1 and 2 (a caller may size the workspace once and run under another
+    setting)."""
     from rollingdepth_amd import _native
 
     lib = _native.lib
-    monkeypatch.delenv("RDMI_ALIGNER_FUSED", raising=False)
     N, P, PS = 14, 9, 8
 
     def size(n, ss, hist):
@@ -167,16 +186,17 @@ def test_start_step_workspace(monkeypatch):
         a.history = C.addressof(keep[-1]) if hist else None
         return lib.rdmi_aligner_workspace(C.byref(a))
 
-    def formula(ntot, hist):  # aligner.hip ws_floats, two-launch loop
+    def formula(ntot, hist):  # csrc/aligner_ws.h
         f = 8 * ntot * PS + 8 * N * PS + 2 * N * P + 4 * ntot + ((ntot + 1) & ~1) + 4 * 21
         if hist:
             f += 20 * (4 * ntot * PS + 2 * N * PS + 2 * ntot) + 2
         return f + 64
 
-    for hist in (False, True):
-        assert size([12, 8], None, hist) == size([12, 8], [1, 1], hist) == formula(20, hist)
-        assert size([7, 5], [2, 2], hist) == formula(12, hist)
-    monkeypatch.setenv("RDMI_ALIGNER_FUSED", "2")
-    for hist in (False, True):
-        assert size([12, 8], None, hist) == size([12, 8], [1, 1], hist) > formula(20, hist)
-        assert size([7, 5], [2, 2], hist) == formula(12, hist)
+    for mode in (None, "0", "1", "2"):
+        if mode is None:
+            monkeypatch.delenv("RDMI_ALIGNER_FUSED", raising=False)
+        else:
+            monkeypatch.setenv("RDMI_ALIGNER_FUSED", mode)
+        for hist in (False, True):
+            assert size([12, 8], None, hist) == size([12, 8], [1, 1], hist) == formula(20, hist), mode
+            assert size([7, 5], [2, 2], hist) == formula(12, hist), mode

@@ -149,21 +149,6 @@ def test_explicit_ones_are_bitwise_the_default(mode, monkeypatch):
         al.run(xs, list(dil), strides=[1, 1])
 
 
-def test_persistent_mode_takes_the_default_loop_when_strided(monkeypatch):
-    """RDMI_ALIGNER_FUSED=2 (the opt-in persistent loop; this shape fits it): a strided job runs the
-    two-launch loop instead, bitwise."""
-    N, dil, lengths, steps = LAYOUTS[0]
-    snips = _synth(N, dil, lengths, steps)
-    monkeypatch.delenv("RDMI_ALIGNER_FUSED", raising=False)
-    a = _device_run(snips, dil, list(steps), N, 140)
-    monkeypatch.setenv("RDMI_ALIGNER_FUSED", "2")
-    b = _device_run(snips, dil, list(steps), N, 140)
-    assert torch.equal(a[0], b[0])
-    for d in range(len(dil)):
-        assert torch.equal(a[1][d], b[1][d]) and torch.equal(a[2][d], b[2][d])
-    assert a[3] == b[3]
-
-
 def test_strided_2000_iterations_vs_reference_golden():
     """The reference's DepthAligner.optimize + merge_scaled_triplets with strided index tensors
     (aligner_strided fixture: N = 20, 64², dilations (1, 4), strides (2, 3)), with the bounds of

@@ -1,9 +1,8 @@
 """Aligner loop A/B at the fast preset's shape (N = 100, dilations [1, 25], 768², 2 000 iterations):
-RDMI_ALIGNER_FUSED = 2 (persistent single launch, opt-in, where it fits), 1 (two launches per iteration,
-the default), 0 (three launches) — outputs compared bitwise against the first value, then timed in
-alternating rounds.
+RDMI_ALIGNER_FUSED = 1 (two launches per iteration, the default), 0 (three launches) — outputs compared
+bitwise against the first value, then timed in alternating rounds.
 
-    python tools/aligner_ab.py [--rounds 3] [--values 1,2]"""
+    python tools/aligner_ab.py [--rounds 3] [--values 0,1]"""
 import argparse
 import os
 import sys
@@ -16,7 +15,7 @@ from rollingdepth_amd import DepthAligner  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=3)
-ap.add_argument("--values", default="1,2")
+ap.add_argument("--values", default="0,1")
 ap.add_argument("--iters", type=int, default=2000)
 a = ap.parse_args()
 vals = a.values.split(",")
