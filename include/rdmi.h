@@ -285,6 +285,23 @@ int rdmi_snippet_accumulate(const void* src, int dtype, int k0, int nloc, int w,
                             int ld, double* sum, void* stream);
 int rdmi_snippet_finish(const double* sum, int n, int w, int stride, int N, long P, int C, int ld, void* out,
                         int dtype, void* stream);
+/* The three refine averaging calls above for a strided refine step (since rdmi_version 4;
+ * csrc/refine_index.h): inside each
+ * residue class of the frames mod `stride` (frames r, r + stride, ...; positions 0, 1, 2, ...) the
+ * snippets start every start_step positions, plus the class's last window when that misses it; src rows
+ * are in class-major order (class ascending, then position).  Slot j of frame f is filled by the snippet
+ * that starts at frame f − j·stride, its row found in closed form (arguments by value, no table in
+ * memory); a frame no snippet covers comes out as zeros.  Sum, division and rounding as above, so
+ * accumulate (any shards, any all-reduce order) + finish reproduce average bitwise, and start_step 1 is
+ * rdmi_snippet_average on the rows sorted by start frame.  1 ≤ start_step ≤ w (a larger step leaves
+ * frames uncovered) and n = the map's snippet count (k0 + nloc ≤ it) are checked, RDMI_E_ARG before any
+ * launch. */
+int rdmi_snippet_average_strided(const void* src, int n, int w, int stride, int start_step, int N, long P, int C,
+                                 int ld, void* out, int dtype, void* stream);
+int rdmi_snippet_accumulate_strided(const void* src, int dtype, int k0, int nloc, int w, int stride, int start_step,
+                                    int N, long P, int C, int ld, double* sum, void* stream);
+int rdmi_snippet_finish_strided(const double* sum, int n, int w, int stride, int start_step, int N, long P, int C,
+                                int ld, void* out, int dtype, void* stream);
 /* Global min/max of an f16 or f32 buffer → minmax[2] f32 (workspace ≥ 2*1024 floats)
  * (the `min([snippet.min() ...])` of depth_aligner.py:78 and the min/max of :316-317). */
 int rdmi_minmax(const void* x, int x_f32, long n, float* minmax, float* workspace, void* stream);

@@ -92,6 +92,9 @@ _SIGS = {
     "rdmi_snippet_average": (i32, [vp, i32, i32, i32, i32, i64, i32, i32, vp, i32, vp]),
     "rdmi_snippet_accumulate": (i32, [vp, i32, i32, i32, i32, i32, i32, i64, i32, i32, vp, vp]),
     "rdmi_snippet_finish": (i32, [vp, i32, i32, i32, i32, i64, i32, i32, vp, i32, vp]),
+    "rdmi_snippet_average_strided": (i32, [vp, i32, i32, i32, i32, i32, i64, i32, i32, vp, i32, vp]),
+    "rdmi_snippet_accumulate_strided": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i64, i32, i32, vp, vp]),
+    "rdmi_snippet_finish_strided": (i32, [vp, i32, i32, i32, i32, i32, i64, i32, i32, vp, i32, vp]),
     "rdmi_colorize": (i32, [vp, i32, i64, vp, vp, i32, vp, vp, vp]),
     "rdmi_resize_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "rdmi_attention_d512": (i32, [vp, vp, vp, vp, i32, i32, i32, i32] + [i64] * 8 + [C.c_float, vp, vp]),

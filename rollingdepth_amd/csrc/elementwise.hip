@@ -1,6 +1,7 @@
 // Layout conversion and small fused elementwise steps of the snippet path (all HBM-bound,
 // grid-stride, 16-B vectors where the channel count allows).
 #include "common.h"
+#include "refine_index.h"
 
 namespace {
 
@@ -181,6 +182,67 @@ __global__ void snippet_finish_k(const double* __restrict__ sum, int n, int w, i
     const int sn = f - j * stride;
     cnt += (sn >= 0 && sn < n) ? 1 : 0;
   }
+  const long tot = P * ld;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
+    const long p = i / ld;
+    const int c = (int)(i - p * ld);
+    float v = 0.f;
+    if (c < C && cnt) v = (float)(sum[((long)f * P + p) * C + c] / (double)cnt);
+    out[(long)f * tot + i] = (T)v;
+  }
+}
+
+// Strided refine (refine_index.h): the snippets start every ss positions inside each residue class of the
+// frames mod `stride`, rows in class-major order.  Slot j of frame f is filled by the snippet that starts
+// at f − j·stride, found by the closed form (block-uniform integers, arguments by value: no table in
+// memory).  Sum, division and rounding are those of the three kernels above.
+template <typename T>
+__global__ void snippet_average_strided_k(const T* __restrict__ src, int w, int stride, int ss, int N, long P, int C,
+                                          int ld, T* __restrict__ out) {
+  const int f = blockIdx.y;
+  const long tot = P * ld;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % ld);
+    float v = 0.f;
+    if (c < C) {
+      double s = 0.0;
+      int cnt = 0;
+      for (int j = w - 1; j >= 0; --j) {  // start frame ascending, as snippet_average_k
+        const int k = rdmi_refine_at(f - j * stride, N, w, stride, ss);
+        if (k < 0) continue;
+        s += (double)(float)src[((long)k * w + j) * tot + i];
+        ++cnt;
+      }
+      v = cnt ? (float)(s / (double)cnt) : 0.f;
+    }
+    out[(long)f * tot + i] = (T)v;
+  }
+}
+
+template <typename T>
+__global__ void snippet_accumulate_strided_k(const T* __restrict__ src, int k0, int nloc, int w, int stride, int ss,
+                                             int N, long P, int C, int ld, double* __restrict__ sum) {
+  const int f = blockIdx.y;
+  const long tot = P * C;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
+    const long p = i / C;
+    const int c = (int)(i - p * C);
+    double s = 0.0;
+    for (int j = w - 1; j >= 0; --j) {
+      const int k = rdmi_refine_at(f - j * stride, N, w, stride, ss);
+      if (k < k0 || k >= k0 + nloc) continue;  // k = -1 (no snippet) < k0
+      s += (double)(float)src[((long)(k - k0) * w + j) * P * ld + p * ld + c];
+    }
+    sum[(long)f * tot + i] = s;
+  }
+}
+
+template <typename T>
+__global__ void snippet_finish_strided_k(const double* __restrict__ sum, int w, int stride, int ss, int N, long P,
+                                         int C, int ld, T* __restrict__ out) {
+  const int f = blockIdx.y;
+  int cnt = 0;
+  for (int j = 0; j < w; ++j) cnt += rdmi_refine_at(f - j * stride, N, w, stride, ss) >= 0 ? 1 : 0;
   const long tot = P * ld;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
     const long p = i / ld;
@@ -442,6 +504,74 @@ extern "C" int rdmi_snippet_finish(const double* sum, int n, int w, int stride, 
     hipLaunchKernelGGL(snippet_finish_k<f16>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream, sum, n, w,
                        stride, P, C, ld, (f16*)out);
   return rdmi::check_launch("snippet_finish");
+}
+
+// the strided refine layout, before any launch: the kernels index src by the closed form, so the row
+// count must be the map's
+static int refine_layout(const char* what, int w, int stride, int start_step, int N) {
+  RDMI_REQUIRE(w > 0 && N > 0 && stride >= 1, RDMI_E_ARG, "%s: bad args (w %d, stride %d, N %d)", what, w, stride, N);
+  RDMI_REQUIRE(start_step >= 1 && start_step <= w, RDMI_E_ARG,
+               "%s: start step %d outside 1 .. %d (the snippet length: a larger step leaves frames uncovered)", what,
+               start_step, w);
+  return 0;
+}
+
+extern "C" int rdmi_snippet_average_strided(const void* src, int n, int w, int stride, int start_step, int N, long P,
+                                            int C, int ld, void* out, int dtype, void* stream) {
+  RDMI_REQUIRE(src && out && n > 0 && ld >= C, RDMI_E_ARG, "snippet_average_strided: bad args");
+  if (int rc = refine_layout("snippet_average_strided", w, stride, start_step, N)) return rc;
+  const int cnt = rdmi_refine_count(N, w, stride, start_step);
+  RDMI_REQUIRE(n == cnt, RDMI_E_ARG, "snippet_average_strided: %d snippets, the index map of N %d w %d stride %d "
+               "start step %d gives %d", n, N, w, stride, start_step, cnt);
+  long tot = P * ld;
+  long gx = (tot + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  if (dtype == RDMI_F32)
+    hipLaunchKernelGGL(snippet_average_strided_k<float>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)src, w, stride, start_step, N, P, C, ld, (float*)out);
+  else
+    hipLaunchKernelGGL(snippet_average_strided_k<f16>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)src, w, stride, start_step, N, P, C, ld, (f16*)out);
+  return rdmi::check_launch("snippet_average_strided");
+}
+
+extern "C" int rdmi_snippet_accumulate_strided(const void* src, int dtype, int k0, int nloc, int w, int stride,
+                                               int start_step, int N, long P, int C, int ld, double* sum,
+                                               void* stream) {
+  RDMI_REQUIRE(sum && ld >= C && k0 >= 0 && nloc >= 0 && (nloc == 0 || src), RDMI_E_ARG,
+               "snippet_accumulate_strided: bad args");
+  if (int rc = refine_layout("snippet_accumulate_strided", w, stride, start_step, N)) return rc;
+  const int cnt = rdmi_refine_count(N, w, stride, start_step);
+  RDMI_REQUIRE(nloc <= cnt && k0 <= cnt - nloc, RDMI_E_ARG, "snippet_accumulate_strided: snippets %d .. %d, the "
+               "index map of N %d w %d stride %d start step %d gives %d", k0, k0 + nloc - 1, N, w, stride, start_step,
+               cnt);
+  long gx = (P * C + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  if (dtype == RDMI_F32)
+    hipLaunchKernelGGL(snippet_accumulate_strided_k<float>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)src, k0, nloc, w, stride, start_step, N, P, C, ld, sum);
+  else
+    hipLaunchKernelGGL(snippet_accumulate_strided_k<f16>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)src, k0, nloc, w, stride, start_step, N, P, C, ld, sum);
+  return rdmi::check_launch("snippet_accumulate_strided");
+}
+
+extern "C" int rdmi_snippet_finish_strided(const double* sum, int n, int w, int stride, int start_step, int N, long P,
+                                           int C, int ld, void* out, int dtype, void* stream) {
+  RDMI_REQUIRE(sum && out && n > 0 && ld >= C, RDMI_E_ARG, "snippet_finish_strided: bad args");
+  if (int rc = refine_layout("snippet_finish_strided", w, stride, start_step, N)) return rc;
+  const int cnt = rdmi_refine_count(N, w, stride, start_step);
+  RDMI_REQUIRE(n == cnt, RDMI_E_ARG, "snippet_finish_strided: %d snippets, the index map of N %d w %d stride %d "
+               "start step %d gives %d", n, N, w, stride, start_step, cnt);
+  long gx = (P * ld + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  if (dtype == RDMI_F32)
+    hipLaunchKernelGGL(snippet_finish_strided_k<float>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream, sum,
+                       w, stride, start_step, N, P, C, ld, (float*)out);
+  else
+    hipLaunchKernelGGL(snippet_finish_strided_k<f16>, dim3((unsigned)gx, N), dim3(256), 0, (hipStream_t)stream, sum,
+                       w, stride, start_step, N, P, C, ld, (f16*)out);
+  return rdmi::check_launch("snippet_finish_strided");
 }
 
 extern "C" int rdmi_colorize(const void* depth, int dtype, long n, const void* minmax, const unsigned char* lut,

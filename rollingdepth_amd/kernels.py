@@ -948,6 +948,45 @@ def snippet_finish(sums: torch.Tensor, n: int, w: int, stride: int, hw, ld: int,
     return out
 
 
+def snippet_average_strided(src: torch.Tensor, stride: int, start_step: int, N: int, c: int = 4) -> torch.Tensor:
+    """snippet_average for a strided refine step: src [n, w, h, wd, ld], rows in the class-major order of
+    pipeline.refine_snippet_indice(N, w, stride, start_step) → [N, h, wd, ld] (rdmi_snippet_average_strided)."""
+    _need_act(src, "snippet_average_strided.src")
+    n, w, h, wd, ld = src.shape
+    src = src.contiguous()
+    out = torch.empty((N, h, wd, ld), dtype=src.dtype, device=src.device)
+    check(lib.rdmi_snippet_average_strided(src.data_ptr(), n, w, stride, start_step, N, h * wd, c, ld, out.data_ptr(),
+                                           _dtype_code(src), _stream()), "rdmi_snippet_average_strided")
+    return out
+
+
+def snippet_accumulate_strided(src: torch.Tensor, k0: int, stride: int, start_step: int, N: int, c: int = 4,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """snippet_accumulate for a strided refine step: src [nloc, w, h, wd, ld] = rows k0 .. k0+nloc-1 of the
+    class-major list → f64 [N, h·wd, c] sums over those rows (zeros elsewhere)."""
+    nloc, w, h, wd, ld = src.shape
+    src = src.contiguous()
+    out = torch.empty((N, h * wd, c), dtype=torch.float64, device=src.device) if out is None else out
+    check(lib.rdmi_snippet_accumulate_strided(src.data_ptr() if nloc else None, _dtype_code(src), k0, nloc, w, stride,
+                                              start_step, N, h * wd, c, ld, out.data_ptr(), _stream()),
+          "rdmi_snippet_accumulate_strided")
+    return out
+
+
+def snippet_finish_strided(sums: torch.Tensor, n: int, w: int, stride: int, start_step: int, hw, ld: int,
+                           dtype=F16) -> torch.Tensor:
+    """snippet_finish for a strided refine step: f64 [N, P, c] all-reduced sums → [N, h, wd, ld] means (÷ the
+    frame's cover count over all n snippets of the class-major list)."""
+    if sums.dtype != torch.float64:
+        raise TypeError("snippet_finish_strided: f64 sums expected (snippet_accumulate_strided)")
+    N, P, c = sums.shape
+    h, wd = hw
+    out = torch.empty((N, h, wd, ld), dtype=dtype, device=sums.device)
+    check(lib.rdmi_snippet_finish_strided(sums.data_ptr(), n, w, stride, start_step, N, P, c, ld, out.data_ptr(),
+                                          _dtype_code(out), _stream()), "rdmi_snippet_finish_strided")
+    return out
+
+
 def minmax(x: torch.Tensor) -> torch.Tensor:
     if x.dtype not in (F16, F32):
         raise TypeError("minmax: f16/f32 expected")

@@ -114,6 +114,61 @@ def _contiguous_range(total: int, world: int, rank: int) -> Tuple[int, int]:
     return min(rank * c, total), min((rank + 1) * c, total)
 
 
+def _class_starts(length: int, snippet_len: int, start_step: int) -> List[int]:
+    """Start positions of the snippets of one residue class of `length` frames: range(0, last + 1, step)
+    plus the last window when the range misses it (csrc/aligner_index.h); none when no window fits."""
+    last = length - snippet_len
+    if last < 0:
+        return []
+    starts = list(range(0, last + 1, start_step))
+    if starts[-1] < last:
+        starts.append(last)
+    return starts
+
+
+def refine_snippet_indice(seq_len: int, snippet_len: int, frame_step: int, start_step: int) -> List[List[int]]:
+    """Snippets of one strided refine step (csrc/refine_index.h): the frames are split into the
+    `frame_step` residue classes r, r + d, r + 2d, …; inside each class the snippets start every
+    `start_step` positions, plus the class's last window when that misses it.  The snippet at position m
+    of class r is the frames r + d·(m + j), j = 0 … snippet_len − 1.  Order: class-major (r ascending,
+    then position).  start_step = 1 gives get_snippet_indice(..., stride=1)'s snippets (sorted by start
+    frame, its order); every start_step ≤ snippet_len covers every frame of every class that holds a
+    snippet.  (get_snippet_indice's own `stride` cannot serve: with a frame step > 1 it leaves frame 1 in
+    no snippet.)"""
+    N, w, d, s = int(seq_len), int(snippet_len), int(frame_step), int(start_step)
+    if N < 1 or w < 1 or d < 1 or s < 1:
+        raise ValueError(f"refine_snippet_indice: seq_len {N}, snippet_len {w}, frame_step {d}, start_step {s}")
+    R = N % d
+    out = []
+    for r in range(d):
+        for m in _class_starts(N // d + (1 if r < R else 0), w, s):
+            out.append([r + d * (m + j) for j in range(w)])
+    return out
+
+
+def refine_snippet_count(seq_len: int, snippet_len: int, frame_step: int, start_step: int) -> int:
+    """len(refine_snippet_indice(...)) in closed form (rdmi_refine_count): the N % d longer classes hold
+    count(N // d + 1 − w) snippets each, the others count(N // d − w)."""
+    N, w, d, s = int(seq_len), int(snippet_len), int(frame_step), int(start_step)
+
+    def count(length):
+        last = length - w
+        return 0 if last < 0 else last // s + 1 + (1 if last % s else 0)
+
+    R = N % d
+    return R * count(N // d + 1) + (d - R) * count(N // d)
+
+
+def check_refine_stride(refine_stride, refine_snippet_len: int) -> int:
+    """`refine_stride` as an int in 1 … refine_snippet_len, or ValueError (bools and non-integers, as
+    `strides` is validated; a step above the snippet length leaves frames in no snippet)."""
+    s = refine_stride
+    if isinstance(s, bool) or not isinstance(s, numbers.Integral) or s < 1 or s > refine_snippet_len:
+        raise ValueError(f"refine_stride must be an int in 1 .. refine_snippet_len ({refine_snippet_len}), "
+                         f"got {refine_stride!r}")
+    return int(s)
+
+
 class RollingDepthPipeline:
     rgb_latent_scale_factor = 0.18215
     depth_latent_scale_factor = 0.18215
@@ -429,7 +484,7 @@ class RollingDepthPipeline:
 
     def refine(self, rgb_latent: torch.Tensor, depth_latents: torch.Tensor, init_noise: torch.Tensor,
                refine_step: int, snippet_len: int, start_dilation: int, skip_t_ratio: float = 0.5,
-               group=None) -> torch.Tensor:
+               group=None, start_step: int = 1, record: Optional[dict] = None) -> torch.Tensor:
         """rollingdepth_pipeline.py:517-633 on device.  rgb_latent / depth_latents NHWC [N,h,w,8]
         (channels 0..3), init_noise NHWC [1,h,w,8].  Returns the refined latents [N,h,w,8].
 
@@ -437,7 +492,14 @@ class RollingDepthPipeline:
         holds all N latents; each step's snippet list is split into W contiguous ranges, each rank runs
         the UNet on its range and sums its predictions per frame, and one all-reduce SUM of the
         [N, h·w, 4] f32 sums (+ the cover count, which is data-independent) gives every rank the
-        step's averaged latents."""
+        step's averaged latents.
+
+        `start_step` > 1 (forward()'s `refine_stride`, 1 … snippet_len): each step denoises the snippets of
+        refine_snippet_indice(N, snippet_len, d, start_step) — the start step taken inside each residue
+        class mod the step's dilation d — and averages them with the strided kernels; 1 is the reference's
+        list.  `record`: per step, the prediction buffer ("refine_pred", this rank's rows) and the averaged
+        latents ("refine_latent") are appended."""
+        start_step = check_refine_stride(start_step, snippet_len)
         world, rank = 1, 0
         if group is not None:
             from .shard import _rank, _world
@@ -456,6 +518,8 @@ class RollingDepthPipeline:
         for i_step, t in enumerate(ts):
             idx = self.get_snippet_indice(i_step, ts, N, snippet_len, start_dilation, 1, 1)
             stride = idx[0][1] - idx[0][0] if snippet_len > 1 else 1
+            if start_step != 1:
+                idx = refine_snippet_indice(N, snippet_len, stride, start_step)
             covered = {f for s in idx for f in s}
             assert len(covered) == N, "refine: every frame must be covered by a snippet"
             lo, hi = _contiguous_range(len(idx), world, rank)
@@ -470,13 +534,25 @@ class RollingDepthPipeline:
                 self.scheduler.step_(pred, int(t), x[..., 4:8], 1.0, channels=4,
                                      out=preds[b0:b0 + len(sel)].view(len(sel) * snippet_len, h, w, 8))
             _progress(f"refine step {i_step + 1}/{len(ts)}: {len(mine)} snippets")
-            if world == 1:
+            if world == 1 and start_step == 1:
                 new = K.snippet_average(preds, stride, N)
+            elif world == 1:
+                new = K.snippet_average_strided(preds, stride, start_step, N)
             else:
                 from .shard import _all_reduce
-                sums = K.snippet_accumulate(preds, lo, stride, N)
+                if start_step == 1:
+                    sums = K.snippet_accumulate(preds, lo, stride, N)
+                else:
+                    sums = K.snippet_accumulate_strided(preds, lo, stride, start_step, N)
                 _all_reduce(sums, group=group)
-                new = K.snippet_finish(sums, len(idx), snippet_len, stride, (h, w), 8, dtype=self.dtype)
+                if start_step == 1:
+                    new = K.snippet_finish(sums, len(idx), snippet_len, stride, (h, w), 8, dtype=self.dtype)
+                else:
+                    new = K.snippet_finish_strided(sums, len(idx), snippet_len, stride, start_step, (h, w), 8,
+                                                   dtype=self.dtype)
+            if record is not None:
+                record.setdefault("refine_pred", []).append(preds)
+                record.setdefault("refine_latent", []).append(new)
         return new
 
     # ------------------------------------------------------------------ entry points
@@ -487,12 +563,15 @@ class RollingDepthPipeline:
                  coalign_kwargs: Union[Dict, None] = None, refine_step: int = 0, refine_snippet_len: int = 3,
                  refine_start_dilation: int = 6, generator: Union[torch.Generator, None] = None,
                  verbose: bool = False, max_vae_bs: int = 4, unload_snippet: bool = False,
-                 restore_res: bool = False, input_fg_video_path=None, **kw) -> RollingDepthOutput:
+                 restore_res: bool = False, input_fg_video_path=None, refine_stride: int = 1,
+                 **kw) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:78-176.  `input_video_path` (or the fork's `input_fg_video_path`):
         a video file (decoding needs PyAV, absent from this image), decoded uint8 rgb24 frames
         [N, H, W, 3] (numpy / torch: resized to processing_res and normalised on the device,
         video_io.load_video_frames), or an already-normalised float [N, 3, H, W] tensor in [-1, 1]
-        (used as is: processing_res and restore_res do not apply to it)."""
+        (used as is: processing_res and restore_res do not apply to it).  `refine_stride` (the build's own,
+        1 … refine_snippet_len): see forward()."""
+        check_refine_stride(refine_stride, refine_snippet_len)
         assert processing_res >= 0
         if processing_res > 1024:
             logging.warning(f"Procssing at high-resolution ({processing_res}) may lead to suboptimal accuracy.")
@@ -514,7 +593,8 @@ class RollingDepthPipeline:
         kw.pop("input_bg_video_path", None)  # fork CLI (run_video.py:563): IC-Light background, unused here
         out = self.forward(frames[None] if frames.dim() == 4 else frames, dilations, cap_dilation, snippet_lengths,
                            init_infer_steps, strides, coalign_kwargs, refine_step, refine_snippet_len,
-                           refine_start_dilation, generator, verbose, max_vae_bs, unload_snippet, **kw)
+                           refine_start_dilation, generator, verbose, max_vae_bs, unload_snippet,
+                           refine_stride=refine_stride, **kw)
         if restore_res:  # rollingdepth_pipeline.py:155-173 (torchvision resize, antialias=True), on the device
             for name in ("input_rgb", "depth_pred"):
                 t = getattr(out, name)
@@ -527,7 +607,8 @@ class RollingDepthPipeline:
         return out
 
     def _forward_sharded(self, input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs, refine_step,
-                         refine_snippet_len, refine_start_dilation, init_noise, record, generator=None, strides=1):
+                         refine_snippet_len, refine_start_dilation, init_noise, record, generator=None, strides=1,
+                         refine_stride: int = 1):
         """forward() over W ranks (shard.sharded_forward), outputs assembled on every rank.  Dilations
         arrive already capped and strides validated (forward's checks ran); the snippets are all-gathered
         at full resolution only here, to honour the snippet_ls contract (bench.py keeps them distributed)."""
@@ -540,7 +621,8 @@ class RollingDepthPipeline:
                              refine_snippet_len=refine_snippet_len, refine_start_dilation=refine_start_dilation,
                              gather=True, record=record, generator=generator,
                              init_infer_steps=list(init_infer_steps),
-                             strides=list(strides) if isinstance(strides, (list, tuple)) else strides)
+                             strides=list(strides) if isinstance(strides, (list, tuple)) else strides,
+                             refine_stride=refine_stride)
         snips = gather_rows_by_dilation([r.to(self.dtype) for r in so.snippet_rows], so.snippet_counts, world,
                                         self._group)
         H, W = so.depth_pred_full.shape[-2:]
@@ -558,7 +640,12 @@ class RollingDepthPipeline:
                 coalign_kwargs: Union[Dict, None], refine_step: int, refine_snippet_len: int,
                 refine_start_dilation: int, generator: Union[torch.Generator, None], verbose: bool,
                 max_vae_bs: int, unload_snippet: bool, init_noise: Optional[torch.Tensor] = None,
-                record: Optional[dict] = None) -> RollingDepthOutput:
+                record: Optional[dict] = None, refine_stride: int = 1) -> RollingDepthOutput:
+        """rollingdepth_pipeline.py:193-353.  `refine_stride` (the build's own, 1 … refine_snippet_len):
+        each refine step starts its snippets that many positions apart inside every residue class mod the
+        step's dilation (refine_snippet_indice), so a frame passes the UNet about refine_snippet_len /
+        refine_stride times per step instead of refine_snippet_len times; 1 is the reference's refine."""
+        refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
         # ----------------- checks (rollingdepth_pipeline.py:214-252)
         assert 1 in dilations, "dilations should include 1"
         assert len(snippet_lengths) == len(set(snippet_lengths)), f"Repeated values found in {snippet_lengths = }"
@@ -610,7 +697,7 @@ class RollingDepthPipeline:
             if dist.get_world_size(self._group) > 1:
                 return self._forward_sharded(input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs,
                                              refine_step, refine_snippet_len, refine_start_dilation, init_noise,
-                                             record, generator, strides)
+                                             record, generator, strides, refine_stride)
         # ----------------- encode (H2D boundary :263)
         frames = input_frames[0].to(self.device)
         # input_rgb = frames / 2 + 0.5 in f16 as the reference computes it on the host (x/2 is exact,
@@ -645,7 +732,8 @@ class RollingDepthPipeline:
         # ----------------- refinement (:323-343, full/paper presets)
         if refine_step > 0:
             dlat = self.encode_rgb(coaligned.expand(-1, 3, -1, -1))
-            new = self.refine(rgb_latent, dlat, noise, refine_step, refine_snippet_len, refine_start_dilation)
+            new = self.refine(rgb_latent, dlat, noise, refine_step, refine_snippet_len, refine_start_dilation,
+                              start_step=refine_stride, record=record)
             if record is not None:
                 record["refined_latent"] = new
             z = K.ddim_combine(new[..., :4], new[..., :4], 1.0 / self.depth_latent_scale_factor, 0.0, 1.0, 4, 8)

@@ -347,7 +347,7 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
                     refine_start_dilation: int = 6, gather: bool = False, record: Optional[dict] = None,
                     generator: Optional[torch.Generator] = None,
                     init_infer_steps: Union[int, Sequence[int]] = 1, timing: Optional[list] = None,
-                    strides: Union[int, Sequence[int]] = 1) -> ShardedOutput:
+                    strides: Union[int, Sequence[int]] = 1, refine_stride: int = 1) -> ShardedOutput:
     """Multi-GPU RollingDepthPipeline.forward (every preset: refine_step > 0 included).
 
     `input_frames` is either the whole video [1,N,3,H,W] / [N,3,H,W], or — with `num_frames=N` —
@@ -363,9 +363,14 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     phase-boundary events (name, torch.cuda.Event) are appended to it (bench.py --slice-world).
     `strides`: frames between the starts of a dilation's consecutive snippets (forward()'s `strides`,
     get_snippet_indice's `stride`; called start steps below), one int >= 1 or one per dilation; the
-    dilations' snippets together must reach every frame (ValueError before any inference, as forward())."""
+    dilations' snippets together must reach every frame (ValueError before any inference, as forward()).
+    `refine_stride`: forward()'s (1 … refine_snippet_len): each rank takes its contiguous range of the
+    step's shorter class-major list (pipeline.refine_snippet_indice)."""
     from . import kernels as K
     from .aligner import DepthAligner, check_row_layout, snippet_count, snippet_last, snippet_start
+    from .pipeline import check_refine_stride
+
+    refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
 
     if group is None:
         group = dist.group.WORLD
@@ -477,7 +482,7 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
             dlat_mine = torch.zeros((0, h, w, pipe.vae.lat_pad), dtype=pipe.dtype, device=dev)
         dlat = _all_gather_rows(dlat_mine, N, world, group)
         new = pipe.refine(rgb_latent, dlat, noise, refine_step, refine_snippet_len, refine_start_dilation,
-                          group=group)
+                          group=group, start_step=refine_stride)
         if record is not None:
             record["refined_latent"] = new
         depth = torch.empty((f1 - f0, H, W, 1), dtype=pipe.depth_dtype, device=dev)

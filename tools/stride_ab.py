@@ -17,6 +17,17 @@ aligner, its strided window sums and finish; every collective a local no-op — 
 does for stride 1).  Per variant: every rank's median step and phases, the slowest rank, and the
 single-GPU step of the same variant.  A rank-slice prediction, not a scaling result: nothing ran on W
 GPUs and the collectives' time is left out.
+
+    python tools/stride_ab.py --refine [--rounds 3] [--frames 100] [--res 512]
+
+measures instead the refine stage's knob, `refine_stride`, on the full preset's structure (dilations
+[1, 10, 25], refine_step 10 from dilation 6, f16, synthetic weights; 512² by default so that the twelve
+forwards finish in a few minutes): refine_stride 1, 2 and 3 interleaved, one warm-up of each, then `rounds`
+rounds.  Per variant: depth frames/s (median, min .. max), the UNet frames of the refine stage and of the
+whole forward, the speed-up the UNet-frame counts alone predict (all UNet frames of the stride-1 forward ÷
+this variant's: the VAE, the aligner and the glue do not shrink), the measured one, the device time of the
+refine stage and — as information only, on random-init weights — the mean |Δ depth_pred| against the
+stride-1 run of the same process.
 """
 import argparse
 import json
@@ -83,15 +94,93 @@ def slice_world(a, pipe, frames, noise, coalign, one):
                       "world": Wd, "frames": N, "res": a.res, "rounds": a.rounds, "rows": rows}))
 
 
+REFINE_VARIANTS = (1, 2, 3)
+
+
+def refine_ab(a, pipe, frames, noise, coalign):
+    """--refine: refine_stride 1, 2, 3 on the full preset's structure, interleaved."""
+    seen = {"all": 0, "refine": 0}
+    events = []
+    unet0, refine0 = pipe.unet.forward, pipe.refine
+    inside = [False]
+
+    def unet(x, *args, **kw):
+        seen["all"] += x.shape[0]
+        if inside[0]:
+            seen["refine"] += x.shape[0]
+        return unet0(x, *args, **kw)
+
+    def refine(*args, **kw):  # device time and UNet frames of the refine stage
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        inside[0] = True
+        e0.record()
+        out = refine0(*args, **kw)
+        e1.record()
+        inside[0] = False
+        events.append((e0, e1))
+        return out
+
+    pipe.unet.forward, pipe.refine = unet, refine
+
+    def one(s):
+        seen.update(all=0, refine=0)
+        events.clear()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = pipe.forward(frames, [1, 10, 25], True, [3], [1], [1], coalign, 10, 3, 6, None, False, 4, False,
+                           init_noise=noise, refine_stride=s)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        return dt, events[0][0].elapsed_time(events[0][1]), out
+
+    res = {s: {"s": [], "refine_ms": []} for s in REFINE_VARIANTS}
+    for s in REFINE_VARIANTS:  # warm-up (and the outputs: every run of a variant computes the same values)
+        _, _, out = one(s)
+        res[s].update(unet_all=seen["all"], unet_refine=seen["refine"], depth=out.depth_pred.float())
+    for r in range(a.rounds):
+        for s in REFINE_VARIANTS:
+            dt, ms, _ = one(s)
+            res[s]["s"].append(dt)
+            res[s]["refine_ms"].append(ms)
+            print(f"round {r} refine_stride {s}: {dt:.3f} s ({a.frames / dt:.2f} depth frames/s), refine stage "
+                  f"{ms:.0f} ms", flush=True)
+    base = res[REFINE_VARIANTS[0]]
+    bmed = statistics.median(base["s"])
+    print("| refine_stride | depth frames/s (median) | min .. max | refine UNet frames | all UNet frames | predicted "
+          "from UNet frames | measured | refine stage ms | mean abs Δ depth_pred |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    rows = []
+    for s in REFINE_VARIANTS:
+        x = res[s]
+        med = statistics.median(x["s"])
+        fps = [a.frames / t for t in x["s"]]
+        dd = (x["depth"] - base["depth"]).abs().mean().item()
+        row = {"refine_stride": s, "frames_per_s": round(a.frames / med, 2), "frames_per_s_min": round(min(fps), 2),
+               "frames_per_s_max": round(max(fps), 2), "unet_frames_refine": x["unet_refine"],
+               "unet_frames_all": x["unet_all"], "predicted_speedup": round(base["unet_all"] / x["unet_all"], 3),
+               "speedup": round(bmed / med, 3), "refine_ms": round(statistics.median(x["refine_ms"]), 1),
+               "mean_abs_ddepth": dd}
+        rows.append(row)
+        print(f"| {s} | {row['frames_per_s']:.2f} | {row['frames_per_s_min']:.2f} .. {row['frames_per_s_max']:.2f} | "
+              f"{row['unet_frames_refine']} | {row['unet_frames_all']} | {row['predicted_speedup']:.3f}x | "
+              f"{row['speedup']:.3f}x | {row['refine_ms']:.0f} | {dd:.2e} |")
+    print(json.dumps({"tool": "stride_ab", "mode": "refine", "frames": a.frames, "res": a.res, "rounds": a.rounds,
+                      "dilations": [1, 10, 25], "refine_step": 10, "rows": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=100)
-    ap.add_argument("--res", type=int, default=768)
+    ap.add_argument("--res", type=int, default=None, help="default 768 (512 with --refine)")
+    ap.add_argument("--refine", action="store_true",
+                    help="A/B refine_stride 1, 2, 3 on the full preset's structure instead of the snippet strides")
     ap.add_argument("--aligner-iters", type=int, default=2000)
     ap.add_argument("--slice-world", type=int, default=0,
                     help="W: time each rank's share of a strided W-rank step on this GPU (shard.SliceGroup)")
     a = ap.parse_args()
+    if a.res is None:
+        a.res = 512 if a.refine else 768
 
     from rollingdepth_amd import aligner as A
     from rollingdepth_amd import config as C
@@ -104,6 +193,8 @@ def main():
     frames = W.synth_frames(a.frames, a.res, a.res, seed=0)[None].to(dev, torch.float16)
     noise = W.synth_noise(a.res // 8, a.res // 8).to(dev)
     coalign = {"num_iterations": a.aligner_iters}
+    if a.refine:
+        return refine_ab(a, pipe, frames, noise, coalign)
 
     events = []
     run0 = A.DepthAligner.run
