@@ -430,6 +430,54 @@ size_t rdmi_resize_workspace(int N, int C, int H, int W, int Ho, int Wo);
 int rdmi_resize(const void* x, int x_dtype, long sn, long sc, long sy, long sx, int N, int C, int H, int W, int Ho,
                 int Wo, int mode, int normalize, float* y, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Depth metrics (since rdmi_version 5): affine-invariant evaluation of a depth video against a target —
+ * the least-squares scale and shift per video or per frame, then AbsRel, SqRel, MAE, RMSE and δ < 1.25ᵏ
+ * on the valid pixels.  The reference ships evaluation split lists (data_split/) and no evaluation code;
+ * this is the protocol its paper reports.
+ *
+ * pred, target [N][P] contiguous, each RDMI_F16 or RDMI_F32 (any element-aligned pointer, any P ≥ 1);
+ * mask [N][P] u8 or NULL.  A pixel is VALID when the mask is absent or ≠ 0 there, pred and target are
+ * finite, and lo < target < hi (hi may be +inf).  All arithmetic is f64, in which the product of two
+ * f16 / f32 values is exact.  workspace ≥ rdmi_depth_metrics_workspace(N, P) doubles, a function of N and P
+ * alone; the three calls share it and run in stream order: moments → fit → errors.
+ *
+ * The summation order is fixed by P alone: a grid of (blocks per frame, N) workgroups whose blocks per
+ * frame depend only on P, a fixed assignment of a frame's pixels to lanes counted from the frame's first
+ * element, a cross-lane butterfly, the waves of a workgroup in wave order, the workgroups of a frame in
+ * block order, and no atomics.  So the sums do not depend on the device, on N, on the other frames, or
+ * on the alignment of the buffers (a frame whose base is not 16-byte aligned is read element by element
+ * in the same assignment instead of with 16-byte loads): repeated calls, and a frame evaluated alone or
+ * inside a video, give the same bits.  N ≤ 65535 (RDMI_E_UNSUPPORTED beyond).
+ *
+ * RDMI_E_ARG before any launch: a null pred / target / workspace / output, N or P < 1, a dtype other than
+ * RDMI_F16 / RDMI_F32, an unknown mode, lo ≥ hi, clip_lo > clip_hi (a NaN bound fails both tests).
+ */
+#define RDMI_FIT_NONE 0  /* (s, t) = (1, 0) */
+#define RDMI_FIT_FRAME 1 /* one fit per frame */
+#define RDMI_FIT_VIDEO 2 /* one fit for all N frames, written into every row */
+long rdmi_depth_metrics_workspace(int N, long P);
+/* Per workgroup, the six sums n, Σp, Σg, Σp², Σpg, Σg² over its valid pixels → workspace. */
+int rdmi_depth_moments(const void* pred, int pred_dtype, const void* target, int target_dtype,
+                       const unsigned char* mask, int N, long P, float lo, float hi, double* workspace, void* stream);
+/* One workgroup.  moments [N][6] (out) = each frame's workspace rows added in block order; st [N][2] (out)
+ * = (s, t) minimising Σ (s·p + t − g)² over the valid pixels: det = n·Σp² − (Σp)², s = (n·Σpg − Σp·Σg) / det,
+ * t = (Σp²·Σg − Σp·Σpg) / det.  RDMI_FIT_FRAME solves per frame; RDMI_FIT_VIDEO adds the frames' moments in
+ * frame order and writes the one solution into every row; n < 2 or det ≤ 0 (of the frame, or in video mode
+ * of the video) gives (NaN, NaN).  RDMI_FIT_NONE writes (1, 0) and needs no moments pass: workspace and
+ * moments may then both be NULL. */
+int rdmi_depth_fit(const double* workspace, int N, long P, int mode, double* moments, double* st, void* stream);
+/* With a = fma(s, p, t) — ONE rounding of s·p + t, which a check against this call has to reproduce —
+ * clamped to [clip_lo, clip_hi] (−inf, +inf: no clip; the target is never clipped), sums [N][8] (out) = per
+ * frame over the valid pixels: n, Σ|a − g|, Σ|a − g|/g, Σ(a − g)², Σ(a − g)²/g (accumulated as
+ * |a − g| · (|a − g|/g)), and the counts of max(a/g, g/a) < 1.25, < 1.25², < 1.25³ (decided as
+ * max(a, g) < c·min(a, g); a ≤ 0 or g ≤ 0 counts as above every threshold).  st [N][2] as written by rdmi_depth_fit; a frame
+ * whose s or t is NaN contributes nothing: its row is zero, n included.  With lo < 0 a valid target may be
+ * ≤ 0 and the two relative sums are then not meaningful (inf / NaN); the others are. */
+int rdmi_depth_errors(const void* pred, int pred_dtype, const void* target, int target_dtype,
+                      const unsigned char* mask, int N, long P, float lo, float hi, const double* st, float clip_lo,
+                      float clip_hi, double* workspace, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
 Public surface mirrors the reference: RollingDepthPipeline / RollingDepthOutput
 (rollingdepth/rollingdepth_pipeline.py), DepthAligner (rollingdepth/depth_aligner.py) and the
-modified diffusers attention processor (CrossFrameAttnProcessor).  All arithmetic runs in
+modified diffusers attention processor (CrossFrameAttnProcessor); depth_metrics / align_scale_shift
+(metrics.py) score a depth video after a least-squares scale and shift.  All arithmetic runs in
 librdmi.so (HIP); importing the compute modules without the built library raises.
 """
 __version__ = "0.1.0"
@@ -18,4 +19,7 @@ def __getattr__(name):
     if name == "CrossFrameAttnProcessor":
         from .attention_processor import CrossFrameAttnProcessor
         return CrossFrameAttnProcessor
+    if name in ("depth_metrics", "align_scale_shift", "DepthMetrics"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(name)

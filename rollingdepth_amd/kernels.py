@@ -1197,3 +1197,76 @@ def resize(x: torch.Tensor, size, mode: str = "BILINEAR", normalize: bool = Fals
     check(lib.rdmi_resize(x.data_ptr(), code, sn, sc, sy, sx, N, Cc, H, W, Ho, Wo, _RESIZE_MODES[mode],
                           int(normalize), out.data_ptr(), _p(ws), _stream()), "rdmi_resize")
     return out
+
+
+# ----------------------------------------------------------------------------- depth metrics
+DEPTH_FIT_MODES = {"none": _N.RDMI_FIT_NONE, "frame": _N.RDMI_FIT_FRAME, "video": _N.RDMI_FIT_VIDEO}
+
+
+def _depth_inputs(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], what: str):
+    """The [N, P] operands of the depth-metric calls: on the device, contiguous, of one shape.  Sizes, dtypes of
+    the library's own codes, ranges and modes are left to librdmi's checks (RDMI_E_ARG → RdmiError)."""
+    for t, name in ((pred, "pred"), (target, "target"), (mask, "mask")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError(f"{what}.{name}: expected a device tensor, got {t.device}")
+        if t.dim() != 2 or t.shape != pred.shape or not t.is_contiguous():
+            raise ValueError(f"{what}.{name}: a contiguous [N, P] tensor of pred's shape expected, got "
+                             f"{tuple(t.shape)} strides {t.stride()}")
+    if mask is not None and mask.dtype != torch.uint8:
+        raise TypeError(f"{what}.mask: uint8 expected, got {mask.dtype}")
+    return pred.shape[0], pred.shape[1]
+
+
+def depth_metrics_workspace(N: int, P: int, device) -> torch.Tensor:
+    """The f64 partials buffer the three depth-metric calls share (its size depends on N and P only)."""
+    return torch.empty(max(int(lib.rdmi_depth_metrics_workspace(N, P)), 1), dtype=torch.float64, device=device)
+
+
+def _depth_ws(ws: Optional[torch.Tensor], N: int, P: int, device) -> torch.Tensor:
+    if ws is None:
+        return depth_metrics_workspace(N, P, device)
+    _need(ws, torch.float64, "depth metrics workspace")
+    if not ws.is_contiguous() or ws.numel() < lib.rdmi_depth_metrics_workspace(N, P):
+        raise ValueError(f"depth metrics workspace: {lib.rdmi_depth_metrics_workspace(N, P)} contiguous f64 "
+                         f"needed, got {ws.numel()}")
+    return ws
+
+
+def depth_moments(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], lo: float, hi: float,
+                  ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-workgroup moment sums of pred / target [N, P] (f16 or f32 each; mask u8 [N, P] or None) over the
+    valid pixels → the workspace depth_fit reads."""
+    N, P = _depth_inputs(pred, target, mask, "depth_moments")
+    ws = _depth_ws(ws, N, P, pred.device)
+    check(lib.rdmi_depth_moments(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target), _p(mask),
+                                 N, P, lo, hi, ws.data_ptr(), _stream()), "rdmi_depth_moments")
+    return ws
+
+
+def depth_fit(ws: Optional[torch.Tensor], N: int, P: int, mode: int, device=None
+              ) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """depth_moments' workspace → (moments f64 [N, 6], st f64 [N, 2]); mode: a DEPTH_FIT_MODES value.  With
+    ws None (mode "none" only) no moments are formed and None is returned for them."""
+    device = ws.device if ws is not None else device
+    st = torch.empty((max(N, 0), 2), dtype=torch.float64, device=device)
+    moments = torch.empty((max(N, 0), 6), dtype=torch.float64, device=device) if ws is not None else None
+    check(lib.rdmi_depth_fit(_p(ws), N, P, mode, _p(moments), st.data_ptr(), _stream()), "rdmi_depth_fit")
+    return moments, st
+
+
+def depth_errors(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], st: torch.Tensor,
+                 lo: float, hi: float, clip_lo: float = -math.inf, clip_hi: float = math.inf,
+                 ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Error sums of fma(s, pred, t) against target → f64 [N, 8] (rdmi.h rdmi_depth_errors); st f64 [N, 2]."""
+    N, P = _depth_inputs(pred, target, mask, "depth_errors")
+    _need(st, torch.float64, "depth_errors.st")
+    if st.shape != (N, 2) or not st.is_contiguous():
+        raise ValueError(f"depth_errors.st: contiguous [N, 2] expected, got {tuple(st.shape)}")
+    ws = _depth_ws(ws, N, P, pred.device)
+    sums = torch.empty((N, 8), dtype=torch.float64, device=pred.device)
+    check(lib.rdmi_depth_errors(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target), _p(mask),
+                                N, P, lo, hi, st.data_ptr(), clip_lo, clip_hi, ws.data_ptr(), sums.data_ptr(),
+                                _stream()), "rdmi_depth_errors")
+    return sums

@@ -7,7 +7,9 @@ refine, synthetic weights) with strides [1, 1], [1, 5] and [2, 5], interleaved: 
 variant, then `rounds` rounds of the three in turn.  Per variant: the snippet counts, the median depth
 frames/s, the run-to-run spread, the aligner time (device time of DepthAligner.run) and — as information
 only — the mean |Δ depth_pred| against the [1, 1] run of the same process (the quality cost of the knob
-on synthetic weights: no bound).  The time base is the [1, 1] run of the same interleave.
+on synthetic weights: no bound), plain and after one least-squares scale and shift of the variant onto the
+[1, 1] run (rollingdepth_amd.metrics.depth_metrics, align="video": the plain mean is mostly the offset that
+depth_pred's renormalisation moves).  The time base is the [1, 1] run of the same interleave.
 
     python tools/stride_ab.py --slice-world 8 [--rounds 2]
 
@@ -27,7 +29,7 @@ rounds.  Per variant: depth frames/s (median, min .. max), the UNet frames of th
 whole forward, the speed-up the UNet-frame counts alone predict (all UNet frames of the stride-1 forward ÷
 this variant's: the VAE, the aligner and the glue do not shrink), the measured one, the device time of the
 refine stage and — as information only, on random-init weights — the mean |Δ depth_pred| against the
-stride-1 run of the same process.
+stride-1 run of the same process, plain and after the video-level fit.
 """
 import argparse
 import json
@@ -41,6 +43,15 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 VARIANTS = ([1, 1], [1, 5], [2, 5])
+
+
+def fitted_mean_abs(variant, base):
+    """mean |s·variant + t − base| with one least-squares (s, t) for the video: the difference that is left
+    when the offset of depth_pred's renormalisation is taken out (every pixel counts: no valid range)."""
+    from rollingdepth_amd.metrics import depth_metrics
+
+    inf = float("inf")
+    return depth_metrics(variant, base, align="video", valid_range=(-inf, inf)).mae
 
 
 def slice_world(a, pipe, frames, noise, coalign, one):
@@ -147,23 +158,24 @@ def refine_ab(a, pipe, frames, noise, coalign):
     base = res[REFINE_VARIANTS[0]]
     bmed = statistics.median(base["s"])
     print("| refine_stride | depth frames/s (median) | min .. max | refine UNet frames | all UNet frames | predicted "
-          "from UNet frames | measured | refine stage ms | mean abs Δ depth_pred |")
-    print("|---|---|---|---|---|---|---|---|---|")
+          "from UNet frames | measured | refine stage ms | mean abs Δ depth_pred | after video fit |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
     rows = []
     for s in REFINE_VARIANTS:
         x = res[s]
         med = statistics.median(x["s"])
         fps = [a.frames / t for t in x["s"]]
         dd = (x["depth"] - base["depth"]).abs().mean().item()
+        df = fitted_mean_abs(x["depth"], base["depth"])
         row = {"refine_stride": s, "frames_per_s": round(a.frames / med, 2), "frames_per_s_min": round(min(fps), 2),
                "frames_per_s_max": round(max(fps), 2), "unet_frames_refine": x["unet_refine"],
                "unet_frames_all": x["unet_all"], "predicted_speedup": round(base["unet_all"] / x["unet_all"], 3),
                "speedup": round(bmed / med, 3), "refine_ms": round(statistics.median(x["refine_ms"]), 1),
-               "mean_abs_ddepth": dd}
+               "mean_abs_ddepth": dd, "mean_abs_ddepth_fitted": df}
         rows.append(row)
         print(f"| {s} | {row['frames_per_s']:.2f} | {row['frames_per_s_min']:.2f} .. {row['frames_per_s_max']:.2f} | "
               f"{row['unet_frames_refine']} | {row['unet_frames_all']} | {row['predicted_speedup']:.3f}x | "
-              f"{row['speedup']:.3f}x | {row['refine_ms']:.0f} | {dd:.2e} |")
+              f"{row['speedup']:.3f}x | {row['refine_ms']:.0f} | {dd:.2e} | {df:.2e} |")
     print(json.dumps({"tool": "stride_ab", "mode": "refine", "frames": a.frames, "res": a.res, "rounds": a.rounds,
                       "dilations": [1, 10, 25], "refine_step": 10, "rows": rows}))
 
@@ -236,22 +248,24 @@ def main():
                   flush=True)
     base = res[tuple(VARIANTS[0])]
     bmed = statistics.median(base["s"])
-    print("| strides | snippets | depth frames/s (median) | min .. max | vs [1, 1] | aligner ms | mean abs Δ depth_pred |")
-    print("|---|---|---|---|---|---|---|")
+    print("| strides | snippets | depth frames/s (median) | min .. max | vs [1, 1] | aligner ms | mean abs Δ depth_pred | "
+          "after video fit |")
+    print("|---|---|---|---|---|---|---|---|")
     rows = []
     for v in VARIANTS:
         x = res[tuple(v)]
         med = statistics.median(x["s"])
         fps = [a.frames / s for s in x["s"]]
         dd = (x["depth"] - base["depth"]).abs().mean().item()
+        df = fitted_mean_abs(x["depth"], base["depth"])
         row = {"strides": v, "snippets": x["counts"], "frames_per_s": round(a.frames / med, 2),
                "frames_per_s_min": round(min(fps), 2), "frames_per_s_max": round(max(fps), 2),
                "speedup": round(bmed / med, 3), "aligner_ms": round(statistics.median(x["aligner_ms"]), 1),
-               "mean_abs_ddepth": dd}
+               "mean_abs_ddepth": dd, "mean_abs_ddepth_fitted": df}
         rows.append(row)
         print(f"| {v} | {' + '.join(map(str, x['counts']))} = {sum(x['counts'])} | {row['frames_per_s']:.2f} | "
               f"{row['frames_per_s_min']:.2f} .. {row['frames_per_s_max']:.2f} | {row['speedup']:.3f}x | "
-              f"{row['aligner_ms']:.1f} | {dd:.2e} |")
+              f"{row['aligner_ms']:.1f} | {dd:.2e} | {df:.2e} |")
     print(json.dumps({"tool": "stride_ab", "frames": a.frames, "res": a.res, "rounds": a.rounds, "rows": rows}))
 
 
