@@ -401,6 +401,42 @@ int rdmi_aligner_merge_finish_pieces_strided(int n_dil, const int* n, const int*
                                              const int* piece_f0, const int* piece_nf, const double* recv,
                                              float* out, void* stream);
 
+/* Merge with the per-pixel spread of the merged terms (since rdmi_version 6).  The covering terms of frame f
+ * and pixel p are a_i = s_k·(x − shift) + t_k, i = 1 … c, exactly the values rdmi_aligner_merge forms in
+ * each x_f32 mode.  mean_out [seq_len][HW] f32 is rdmi_aligner_merge's out, bitwise; std_out [seq_len][HW]
+ * f32 is their population standard deviation sqrt(max(0, Σa²/c − (Σa/c)²)): Σa and Σa² accumulated in f64
+ * in the merge's (d, j) order, evaluated in f64 and rounded once, 0 where c ≤ 1.  One pass over the
+ * snippets.  With HW % 4 == 0 and every base pointer (snippets, outputs) 16-byte aligned a lane takes 4
+ * consecutive pixels with 16-byte loads (8-byte for f16 rows); otherwise one pixel per lane.
+ * These calls always take start steps (all ones: snippets start at every frame), every one ≥ 1, and always
+ * check the layout against the index map before any launch (the checks of rdmi_aligner_merge_strided): a
+ * start step < 1, a window that does not fit seq_len, an n_d other than the map's count or a null output
+ * → RDMI_E_ARG.  Σ w_d ≤ 64 (RDMI_E_UNSUPPORTED beyond).
+ * Sharded form: rdmi_aligner_merge_partial_window_moments writes mom_out [nf][2][HW] f64 — per frame Σa
+ * then Σa² over the rank's rows (k0 / nloc as rdmi_aligner_merge_partial_window; in mode 0 Σa is the f64
+ * sum of the f16-rounded terms) — so a frame stays one row of the all-to-all; and
+ * rdmi_aligner_merge_finish_pieces_moments adds the received pieces recv [Σ piece_nf][2][HW] per frame
+ * in source-rank order for both moments, divides by the cover count and writes mean and std (piece tables
+ * wider than 64 are split by frame range as in rdmi_aligner_merge_finish_pieces; nf = 0 needs no outputs).
+ * The means reproduce rdmi_aligner_merge as the sharded merge does; the f64 sums of squares can depend on
+ * the order of addition in their last bits. */
+int rdmi_aligner_merge_moments(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                               const float* const* t, const int* n, const int* stride, const int* start_step,
+                               const int* w, int seq_len, long HW, const float* shift, float* mean_out,
+                               float* std_out, void* stream);
+int rdmi_aligner_merge_partial_window_moments(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                                              const float* const* t, const int* n, const int* stride,
+                                              const int* start_step, const int* k0, const int* nloc, const int* w,
+                                              int seq_len, int f0, int nf, long HW, const float* shift,
+                                              double* mom_out, void* stream);
+int rdmi_aligner_merge_finish_pieces_moments(int n_dil, const int* n, const int* stride, const int* start_step,
+                                             const int* w, int seq_len, int f0, int nf, long HW, int npieces,
+                                             const int* piece_f0, const int* piece_nf, const double* recv,
+                                             float* mean_out, float* std_out, void* stream);
+/* In place: x = (x / (mx − mn)) · 2 with mn, mx read from the device — rdmi_renormalize_f32 without its
+ * offsets: a spread of the merged map in the units of the renormalised one (since rdmi_version 6). */
+int rdmi_scale_spread_f32(float* x, long n, const float* minmax, void* stream);
+
 /* Single-head flash attention for head dim 512 (f16): the VAE mid-block attention
  * (unet_2d_blocks.py:680-697 through AttnProcessor2_0's 4-D path, attention_processor.py:2172-2276 —
  * one head, d = C = 512) as one pass over K / Vᵀ instead of f32 scores → softmax → PV.

@@ -105,7 +105,7 @@ class DepthAligner:
         return scales, trans, hist, ws
 
     def run(self, snippet_ls: List[torch.Tensor], dilations: List[int], strides: Optional[List[int]] = None,
-            sequence_length: Optional[int] = None, merged_f32: bool = False):
+            sequence_length: Optional[int] = None, merged_f32: bool = False, uncertainty: bool = False):
         """depth_aligner.py:68-120.  merged_f32=True (the pipeline's internal use): the merge of f16
         snippets runs in f32 arithmetic and is returned in f32, without the reference's f16 roundings
         of s·x+t and of the merged map (RollingDepthPipeline.merge_f32).
@@ -117,7 +117,15 @@ class DepthAligner:
 
         strides (one per dilation, or one for all): the snippets of a dilation start that many frames
         apart, plus the last window (get_snippet_indice's `stride`).  sequence_length is then required —
-        a snippet count no longer determines it.  Without strides everything is as above."""
+        a snippet count no longer determines it.  Without strides everything is as above.
+
+        uncertainty=True (the build's own): the merge also keeps how far the merged terms lie apart
+        (kernels.aligner_merge_moments in place of aligner_merge, same merged map bitwise) and a fifth
+        element is returned: the per-pixel population standard deviation of a frame's covering terms
+        s·(x − min) + t, [N, 1, H, W] f32 in the units of the merged map before any renormalisation, 0
+        where fewer than two snippets cover a frame."""
+        if not isinstance(uncertainty, bool):
+            raise TypeError(f"uncertainty must be a bool, got {type(uncertainty).__name__}")
         dev = torch.device(self.device)
         snippet_ls = [s.to(dev) for s in snippet_ls]
         lengths = [s.shape[1] for s in snippet_ls]
@@ -147,9 +155,15 @@ class DepthAligner:
         xs = self.prepare(flat, shift)
         frame_steps = [g + 1 for g in gaps]
         scales, trans, hist, ws = self.optimize_prepared(xs, frame_steps, seq_len, start_steps)
-        merged = K.aligner_merge(flat, scales, trans, frame_steps, seq_len, shift, f32_arith=merged_f32,
-                                 start_steps=start_steps)
+        spread = None
+        if uncertainty:
+            merged, spread = K.aligner_merge_moments(flat, scales, trans, frame_steps, seq_len, shift,
+                                                     f32_arith=merged_f32, start_steps=start_steps)
+        else:
+            merged = K.aligner_merge(flat, scales, trans, frame_steps, seq_len, shift, f32_arith=merged_f32,
+                                     start_steps=start_steps)
         merged = (merged if merged_f32 else merged.to(dtype))[:, None]
         loss_ls = [tuple(r) for r in hist[: self.num_iterations].tolist()]
         del ws
-        return (merged, [s.view(-1, 1, 1) for s in scales], [t.view(-1, 1, 1) for t in trans], loss_ls)
+        res = (merged, [s.view(-1, 1, 1) for s in scales], [t.view(-1, 1, 1) for t in trans], loss_ls)
+        return res + (spread[:, None],) if uncertainty else res

@@ -15,6 +15,8 @@
 //                  mul+addcmul, sqrt/bc2_sqrt + eps, addcdiv), loss history row.
 // merge        — merge_scaled_triplets (:231-262): per frame the mean over all covering slots of
 //                s·x+t, rounded through the snippet dtype where the reference computes in it.
+// merge_moments — the same mean plus the per-pixel standard deviation of those slots' terms, in one pass
+//                (the build's own; end of this file).
 //
 // Snippet lengths may differ per dilation (rollingdepth_pipeline.py:221-226).  The reference then
 // scatters dilation i's slot j into row i·w_i + j of its [Σw, N, P] tensors M / M_depth / B
@@ -931,4 +933,372 @@ extern "C" int rdmi_aligner_merge_finish_pieces_strided(int n_dil, const int* n,
                "aligner_merge_finish_pieces_strided: frames %d+%d outside the %d of the sequence", f0, nf, seq_len);
   return finish_pieces_launch(n_dil, n, stride, w, f0, nf, HW, npieces, piece_f0, piece_nf, recv, out, stream,
                               start_step, seq_len);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Merge with the per-pixel spread of the merged terms (since rdmi_version 6).  A frame's covering terms
+// a_i = s_k·(x − shift) + t_k, i = 1 … c, are the values merge_k forms in each x_f32 mode, visited in
+// its (d ascending, j descending) order; beside their mean the kernels below keep Σa and Σa² in f64
+// (a² of an f32 a is exact in f64) and write the population standard deviation
+//   sqrt(max(0, Σa²/c − (Σa/c)²)),  evaluated in f64 and rounded once to f32,  0 where c ≤ 1.
+// The f64 accumulation error of both sums is at most (c + 4)·2⁻⁵²·max a² in the variance.
+// The mean is merge_k's, bitwise: f64 sum ÷ c rounded once in modes 1 / 2, the f32 running sum in mode 0
+// (whose spread still comes from f64 sums of the same f16-rounded terms).
+//
+// An HBM-bound stream: every snippet pixel is read once.  Which snippet covers frame f in slot (d, j) is the
+// same for the whole block, so the first wave resolves it once per block into an LDS table (row pointer,
+// s, t), compacted in merge_k's order by a ballot; the pixel loop then only walks that table.  On the
+// vector path (HW % 4 == 0, every base pointer 16-byte aligned) a lane owns 4 consecutive pixels: 16-byte
+// loads of f32 rows, 8-byte loads of f16 rows, up to MOM_U rows' loads issued before the first is used.
+namespace {
+
+constexpr int MOM_U = 8;  // table rows whose loads are issued together (the fast preset has ≤ 6 per frame)
+// Pixel groups per thread the grid is sized for: a block resolves its frame's table once for 4 · 256 groups.
+// 100 × 768² f32, 98 + 50 snippets: 0.307 ms for 2 and 4, 0.314 for 8, 0.341 for 1 (profiles/merge_moments_probe.log)
+constexpr int MOM_ITER = 4;
+
+struct MomP {
+  MergeP m;        // out = the mean (fused form); dsum unused
+  float* std_out;  // fused form
+  double* mom;     // sum-only form: [nf][2][HW], Σa then Σa² per frame (NULL: fused form)
+};
+
+struct MomEnt {
+  const char* row;  // the covering snippet's slot row [HW]
+  float s, t;
+};
+
+// The covering (d, j) of frame f among the rows this call holds, in merge_k's order → tab[0 .. c).
+// Σ w_d ≤ MAXR = 64: one lane of the first wave per (d, j).
+template <bool SS>
+__device__ __forceinline__ int moments_table(const MergeP& p, int f, MomEnt* tab, int* cnt) {
+  if (threadIdx.x < 64) {
+    const int i = threadIdx.x;
+    const int esz = p.xf32 == 1 ? 4 : 2;
+    bool ok = false;
+    MomEnt e{nullptr, 0.f, 0.f};
+    int base = 0;
+    for (int d = 0; d < p.nd; ++d) {  // d is uniform: the job's fields are read with scalar indices
+      const int r = i - base;
+      base += p.w[d];
+      if (r < 0 || r >= p.w[d]) continue;
+      const int j = p.w[d] - 1 - r;
+      const int q = f - j * p.stride[d];
+      const int k = SS ? rdmi_snip_at(q, p.ss[d], p.last[d], p.n[d]) : q;
+      if (k < p.k0[d] || k >= p.k0[d] + p.nloc[d]) continue;
+      ok = true;
+      e.row = (const char*)p.x[d] + ((long)(k - p.k0[d]) * p.w[d] + j) * p.HW * esz;
+      e.s = p.s[d][k];
+      e.t = p.t[d][k];
+    }
+    const unsigned long long mask = __ballot(ok);
+    if (ok) tab[__popcll(mask & ((1ull << i) - 1ull))] = e;
+    if (i == 0) *cnt = __popcll(mask);
+  }
+  __syncthreads();
+  return __builtin_amdgcn_readfirstlane(*cnt);
+}
+
+// V consecutive pixels of a row, from pixel px on, as f32 (the f16 → f32 conversion is exact)
+template <int V, bool XF32>
+__device__ __forceinline__ void mom_load(const char* row, long px, float (&v)[V]) {
+  if constexpr (XF32) {
+    const float* r = (const float*)row + px;
+    if constexpr (V == 4) {
+      const f32x4 x = *(const f32x4*)r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = x[e];
+    } else {
+      v[0] = r[0];
+    }
+  } else {
+    const f16* r = (const f16*)row + px;
+    if constexpr (V == 4) {
+      const f16x4 x = *(const f16x4*)r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (float)x[e];
+    } else {
+      v[0] = (float)r[0];
+    }
+  }
+}
+
+// One term, exactly as merge_k forms it.  In the f32 modes that is ONE rounding of s·(x − shift) + t: hipcc
+// compiles merge_k's addrn(mulrn(xs, s), t) to a single v_fmac_f32 (the __f*_rn intrinsics do not keep the
+// product's rounding, the file's `fp contract(off)` notwithstanding), so the fused multiply-add is written
+// out here; the mean's bitwise tests against merge_k hold the two together.
+__device__ __forceinline__ float mom_term(float x, float sh, float s, float t, bool f16_chain) {
+  if (!f16_chain) return __builtin_fmaf(x - sh, s, t);
+  const f16 xs = (f16)(x - sh);
+  const f16 sc = (f16)s, tr = (f16)t;
+  const f16 prod = (f16)((float)xs * (float)sc);
+  return (float)(f16)((float)prod + (float)tr);
+}
+
+__device__ __forceinline__ float mom_std(double s1, double s2, int c) {
+  if (c <= 1) return 0.f;
+  const double m1 = s1 / (double)c, m2 = s2 / (double)c;
+  const double var = m2 - m1 * m1;
+  return (float)sqrt(var > 0.0 ? var : 0.0);
+}
+
+template <bool SS, int V, bool XF32>
+__global__ __launch_bounds__(256) void merge_moments_k(MomP pp) {
+  __shared__ MomEnt tab[MAXR];
+  __shared__ int cnt_sh;
+  const MergeP& p = pp.m;
+  const int fl = blockIdx.y, f = p.f0 + fl;
+  const int c = moments_table<SS>(p, f, tab, &cnt_sh);
+  const float sh = p.shift ? p.shift[0] : 0.f;
+  const bool chain = p.xf32 == 0;
+  const long groups = p.HW / V;  // V == 4 only when HW % 4 == 0
+  for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < groups; g += (long)gridDim.x * blockDim.x) {
+    const long px = g * V;
+    float sum[V];
+    double s1[V], s2[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) sum[v] = 0.f, s1[v] = 0.0, s2[v] = 0.0;
+    for (int e0 = 0; e0 < c; e0 += MOM_U) {
+      float x[MOM_U][V];
+#pragma unroll
+      for (int u = 0; u < MOM_U; ++u)
+        if (e0 + u < c) mom_load<V, XF32>(tab[e0 + u].row, px, x[u]);
+#pragma unroll
+      for (int u = 0; u < MOM_U; ++u)
+        if (e0 + u < c) {
+          const float s = tab[e0 + u].s, t = tab[e0 + u].t;
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            const float a = mom_term(x[u][v], sh, s, t, chain);
+            const double ad = (double)a;
+            sum[v] = addrn(sum[v], a);
+            s1[v] += ad;
+            s2[v] += ad * ad;
+          }
+        }
+    }
+    if (pp.mom) {
+      double* o1 = pp.mom + ((long)fl * 2) * p.HW + px;
+      double* o2 = o1 + p.HW;
+      if constexpr (V == 4) {
+        typedef double f64x2 __attribute__((ext_vector_type(2)));
+        *(f64x2*)o1 = f64x2{s1[0], s1[1]};
+        *(f64x2*)(o1 + 2) = f64x2{s1[2], s1[3]};
+        *(f64x2*)o2 = f64x2{s2[0], s2[1]};
+        *(f64x2*)(o2 + 2) = f64x2{s2[2], s2[3]};
+      } else {
+        o1[0] = s1[0];
+        o2[0] = s2[0];
+      }
+    } else {
+      float mean[V], sd[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        mean[v] = chain ? (c ? sum[v] / (float)c : 0.f) : (c ? (float)(s1[v] / (double)c) : 0.f);
+        sd[v] = mom_std(s1[v], s2[v], c);
+      }
+      const long o = (long)fl * p.HW + px;
+      if constexpr (V == 4) {
+        *(f32x4*)(p.out + o) = f32x4{mean[0], mean[1], mean[2], mean[3]};
+        *(f32x4*)(pp.std_out + o) = f32x4{sd[0], sd[1], sd[2], sd[3]};
+      } else {
+        p.out[o] = mean[0];
+        pp.std_out[o] = sd[0];
+      }
+    }
+  }
+}
+
+// merge_finish_pieces_k for the two moments: recv holds [2][HW] per frame of a piece (q.poff counts
+// doubles), both added per frame in piece (= source rank) order, ÷ the frame's cover count.
+template <bool SS>
+__global__ void merge_finish_moments_k(MergeP p, PiecesP q, const double* __restrict__ recv, float* std_out) {
+  const int fl = blockIdx.y, f = p.f0 + fl;
+  const int cnt = SS ? rdmi_cover_count(p.nd, p.n, p.stride, p.w, p.ss, p.last, f)
+                     : cover_count(p.n, p.stride, p.nd, p.w, f);
+  for (long px = blockIdx.x * (long)blockDim.x + threadIdx.x; px < p.HW; px += (long)gridDim.x * blockDim.x) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < q.np; ++i)
+      if (f >= q.pf0[i] && f < q.pf0[i] + q.pnf[i]) {
+        const double* r = recv + q.poff[i] + (long)(f - q.pf0[i]) * 2 * p.HW + px;
+        s1 += r[0];
+        s2 += r[p.HW];
+      }
+    p.out[(long)fl * p.HW + px] = cnt ? (float)(s1 / (double)cnt) : 0.f;
+    std_out[(long)fl * p.HW + px] = mom_std(s1, s2, cnt);
+  }
+}
+
+// The start steps of a moments call: always given, every one ≥ 1 (all ones: start step 1), and the layout
+// always checked against the index map before any launch.
+int moments_start_steps(const char* what, int nd, const int* start_step, const int* n, const int* stride,
+                        const int* w, int N, int* ss, int* last, bool* strided) {
+  *strided = false;
+  for (int d = 0; d < nd; ++d) {
+    RDMI_REQUIRE(start_step[d] >= 1, RDMI_E_ARG, "%s: start step %d of dilation %d (>= 1 expected)", what,
+                 start_step[d], d);
+    ss[d] = start_step[d];
+    if (ss[d] > 1) *strided = true;
+    RDMI_REQUIRE(stride[d] >= 1 && w[d] >= 1, RDMI_E_ARG, "%s: dilation %d: length %d, frame stride %d", what, d, w[d],
+                 stride[d]);
+    last[d] = rdmi_snip_last(N, w[d], stride[d]);
+    RDMI_REQUIRE(last[d] >= 0, RDMI_E_ARG,
+                 "%s: dilation %d: a snippet of length %d and frame stride %d does not fit %d frames", what, d, w[d],
+                 stride[d], N);
+    const int want = rdmi_snip_count(last[d], ss[d]);
+    RDMI_REQUIRE(n[d] == want, RDMI_E_ARG,
+                 "%s: dilation %d: %d snippets, but start step %d over %d frames (length %d, frame stride %d) gives %d",
+                 what, d, n[d], ss[d], N, w[d], stride[d], want);
+  }
+  return 0;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int moments_launch(const char* what, int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                   const float* const* t, const int* n, const int* stride, const int* start_step, const int* k0,
+                   const int* nloc, const int* w, int seq_len, int f0, int nf, long HW, const float* shift,
+                   float* mean_out, float* std_out, double* mom_out, void* stream) {
+  RDMI_REQUIRE(n_dil >= 1 && n_dil <= MAXD && xf && s && t && n && stride && start_step && w && HW > 0 &&
+                   seq_len > 0 && x_f32 >= 0 && x_f32 <= 2,
+               RDMI_E_ARG, "%s: bad args", what);
+  RDMI_REQUIRE(f0 >= 0 && nf >= 0 && f0 <= seq_len && nf <= seq_len - f0, RDMI_E_ARG,
+               "%s: frames %d+%d outside the %d of the sequence", what, f0, nf, seq_len);
+  MomP pp{};
+  MergeP& p = pp.m;
+  int rows = 0;
+  for (int d = 0; d < n_dil; ++d) {
+    const int kk = k0 ? k0[d] : 0, nl = nloc ? nloc[d] : n[d];
+    RDMI_REQUIRE(kk >= 0 && nl >= 0 && kk + nl <= n[d] && w[d] >= 1 && (nl == 0 || (xf[d] && s[d] && t[d])),
+                 RDMI_E_ARG, "%s: dilation %d rows %d+%d of %d, length %d", what, d, kk, nl, n[d], w[d]);
+    p.x[d] = xf[d];
+    p.s[d] = s[d];
+    p.t[d] = t[d];
+    p.n[d] = n[d];
+    p.stride[d] = stride[d];
+    p.k0[d] = kk;
+    p.nloc[d] = nl;
+    p.w[d] = w[d];
+    rows += w[d];
+  }
+  RDMI_REQUIRE(rows <= MAXR, RDMI_E_UNSUPPORTED, "%s: snippet lengths sum to %d (at most %d)", what, rows, MAXR);
+  p.nd = n_dil; p.xf32 = x_f32; p.HW = HW; p.shift = shift; p.out = mean_out; p.f0 = f0;
+  pp.std_out = std_out;
+  pp.mom = mom_out;
+  bool strided = false;
+  if (int rc = moments_start_steps(what, n_dil, start_step, p.n, p.stride, p.w, seq_len, p.ss, p.last, &strided))
+    return rc;
+  if (nf == 0) return 0;
+  bool vec = HW % 4 == 0 && aligned16(mean_out) && aligned16(std_out) && aligned16(mom_out);
+  for (int d = 0; d < n_dil; ++d) vec = vec && (p.nloc[d] == 0 || aligned16(p.x[d]));
+  const long groups = vec ? HW / 4 : HW;
+  long gx = (groups + 256 * MOM_ITER - 1) / (256 * MOM_ITER);
+  if (gx > 1024) gx = 1024;
+  const dim3 grid((unsigned)gx, nf), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+#define RDMI_MOM_LAUNCH(SS_, V_, F32_) hipLaunchKernelGGL((merge_moments_k<SS_, V_, F32_>), grid, blk, 0, st, pp)
+#define RDMI_MOM_PICK(SS_)                           \
+  do {                                               \
+    if (vec && x_f32 == 1) RDMI_MOM_LAUNCH(SS_, 4, true);       \
+    else if (vec) RDMI_MOM_LAUNCH(SS_, 4, false);    \
+    else if (x_f32 == 1) RDMI_MOM_LAUNCH(SS_, 1, true);         \
+    else RDMI_MOM_LAUNCH(SS_, 1, false);             \
+  } while (0)
+  if (strided)
+    RDMI_MOM_PICK(true);
+  else
+    RDMI_MOM_PICK(false);
+#undef RDMI_MOM_PICK
+#undef RDMI_MOM_LAUNCH
+  return rdmi::check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int rdmi_aligner_merge_moments(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                                          const float* const* t, const int* n, const int* stride,
+                                          const int* start_step, const int* w, int seq_len, long HW,
+                                          const float* shift, float* mean_out, float* std_out, void* stream) {
+  RDMI_REQUIRE(mean_out && std_out, RDMI_E_ARG, "aligner_merge_moments: null output");
+  return moments_launch("aligner_merge_moments", n_dil, xf, x_f32, s, t, n, stride, start_step, nullptr, nullptr, w,
+                        seq_len, 0, seq_len, HW, shift, mean_out, std_out, nullptr, stream);
+}
+
+extern "C" int rdmi_aligner_merge_partial_window_moments(int n_dil, const void* const* xf, int x_f32,
+                                                         const float* const* s, const float* const* t, const int* n,
+                                                         const int* stride, const int* start_step, const int* k0,
+                                                         const int* nloc, const int* w, int seq_len, int f0, int nf,
+                                                         long HW, const float* shift, double* mom_out, void* stream) {
+  RDMI_REQUIRE(k0 && nloc && mom_out, RDMI_E_ARG, "aligner_merge_partial_window_moments: k0/nloc/mom_out required");
+  return moments_launch("aligner_merge_partial_window_moments", n_dil, xf, x_f32, s, t, n, stride, start_step, k0,
+                        nloc, w, seq_len, f0, nf, HW, shift, nullptr, nullptr, mom_out, stream);
+}
+
+extern "C" int rdmi_aligner_merge_finish_pieces_moments(int n_dil, const int* n, const int* stride,
+                                                        const int* start_step, const int* w, int seq_len, int f0,
+                                                        int nf, long HW, int npieces, const int* piece_f0,
+                                                        const int* piece_nf, const double* recv, float* mean_out,
+                                                        float* std_out, void* stream) {
+  const char* what = "aligner_merge_finish_pieces_moments";
+  RDMI_REQUIRE(n_dil >= 1 && n_dil <= MAXD && n && stride && start_step && w && HW > 0 && seq_len > 0 &&
+                   npieces >= 0 && (npieces == 0 || (piece_f0 && piece_nf && recv)),
+               RDMI_E_ARG, "%s: bad args", what);
+  RDMI_REQUIRE(f0 >= 0 && nf >= 0 && f0 <= seq_len && nf <= seq_len - f0, RDMI_E_ARG,
+               "%s: frames %d+%d outside the %d of the sequence", what, f0, nf, seq_len);
+  RDMI_REQUIRE((mean_out && std_out) || nf == 0, RDMI_E_ARG, "%s: null output", what);
+  MergeP p{};
+  for (int d = 0; d < n_dil; ++d) {
+    p.n[d] = n[d];
+    p.stride[d] = stride[d];
+    p.w[d] = w[d];
+  }
+  p.nd = n_dil; p.HW = HW;
+  bool strided = false;
+  if (int rc = moments_start_steps(what, n_dil, start_step, p.n, p.stride, p.w, seq_len, p.ss, p.last, &strided))
+    return rc;
+  for (int i = 0; i < npieces; ++i)
+    RDMI_REQUIRE(piece_nf[i] >= 0 && piece_f0[i] >= f0 && piece_f0[i] + piece_nf[i] <= f0 + nf, RDMI_E_ARG,
+                 "%s: piece %d frames %d+%d outside %d+%d", what, i, piece_f0[i], piece_nf[i], f0, nf);
+  if (nf == 0) return 0;
+  // A piece table wider than MAXPIECES is split by frame range, as rdmi_aligner_merge_finish_pieces does:
+  // every frame still adds all of its pieces in source-rank order within one thread.
+  auto touches = [&](int i, int a, int b) { return piece_nf[i] > 0 && piece_f0[i] < b && piece_f0[i] + piece_nf[i] > a; };
+  long gx = (HW + 255) / 256;
+  if (gx > 1024) gx = 1024;
+  int fs = f0;
+  while (fs < f0 + nf) {
+    int fe = fs + 1, cnt = 0;
+    for (int i = 0; i < npieces; ++i) cnt += touches(i, fs, fe);
+    RDMI_REQUIRE(cnt <= MAXPIECES, RDMI_E_UNSUPPORTED, "%s: frame %d is covered by %d pieces (at most %d)", what, fs,
+                 cnt, MAXPIECES);
+    while (fe < f0 + nf) {
+      int c2 = 0;
+      for (int i = 0; i < npieces; ++i) c2 += touches(i, fs, fe + 1);
+      if (c2 > MAXPIECES) break;
+      ++fe;
+    }
+    PiecesP q{};
+    long off = 0;
+    for (int i = 0; i < npieces; ++i) {
+      if (touches(i, fs, fe)) {
+        q.pf0[q.np] = piece_f0[i];
+        q.pnf[q.np] = piece_nf[i];
+        q.poff[q.np] = off;
+        ++q.np;
+      }
+      off += (long)piece_nf[i] * 2 * HW;
+    }
+    p.f0 = fs;
+    p.out = mean_out + (long)(fs - f0) * HW;
+    float* sd = std_out + (long)(fs - f0) * HW;
+    if (strided)
+      hipLaunchKernelGGL(merge_finish_moments_k<true>, dim3((unsigned)gx, fe - fs), dim3(256), 0, (hipStream_t)stream,
+                         p, q, recv, sd);
+    else
+      hipLaunchKernelGGL(merge_finish_moments_k<false>, dim3((unsigned)gx, fe - fs), dim3(256), 0, (hipStream_t)stream,
+                         p, q, recv, sd);
+    if (int rc = rdmi::check_launch(what)) return rc;
+    fs = fe;
+  }
+  return 0;
 }

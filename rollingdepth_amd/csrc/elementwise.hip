@@ -354,6 +354,15 @@ __global__ void renorm_k(float* __restrict__ x, long n, const float* __restrict_
   }
 }
 
+// renorm_k without its offsets: a spread in the merged map's units → the units of the renormalised map
+__global__ void scale_spread_k(float* __restrict__ x, long n, const float* __restrict__ mm) {
+  const float rng = mm[1] - mm[0];
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float v = x[i] / rng;
+    x[i] = v * 2.0f;
+  }
+}
+
 }  // namespace
 
 extern "C" int rdmi_nchw_to_nhwc(const void* x, int x_f32, void* y, int y_dtype, int B, int C, int H, int W, int Cpad,
@@ -460,6 +469,12 @@ extern "C" int rdmi_renormalize_f32(float* x, long n, const float* minmax, void*
   RDMI_REQUIRE(x && minmax && n > 0, RDMI_E_ARG, "renormalize: bad args");
   hipLaunchKernelGGL(renorm_k, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, n, minmax);
   return rdmi::check_launch("renormalize");
+}
+
+extern "C" int rdmi_scale_spread_f32(float* x, long n, const float* minmax, void* stream) {
+  RDMI_REQUIRE(x && minmax && n > 0, RDMI_E_ARG, "scale_spread: bad args");
+  hipLaunchKernelGGL(scale_spread_k, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, n, minmax);
+  return rdmi::check_launch("scale_spread");
 }
 
 extern "C" int rdmi_snippet_average(const void* src, int n, int w, int stride, int N, long P, int C, int ld, void* out,

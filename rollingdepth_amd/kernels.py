@@ -1157,6 +1157,100 @@ def aligner_merge_finish_pieces(recv: torch.Tensor, pieces: Sequence[Tuple[int, 
     return out
 
 
+def _ones_or(what: str, start_steps: Optional[Sequence[int]], nd: int):
+    """The start steps of a moments call (they always travel; None: all ones) as a C int array."""
+    if start_steps is None:
+        start_steps = [1] * nd
+    if len(start_steps) != nd:
+        raise ValueError(f"{what}: {len(start_steps)} start steps for {nd} dilations")
+    return (C.c_int * nd)(*[int(v) for v in start_steps])
+
+
+def aligner_merge_moments(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: int, shift: torch.Tensor,
+                          f32_arith: bool = False, start_steps: Optional[Sequence[int]] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aligner_merge that also returns the spread of the merged terms (rdmi_aligner_merge_moments): xf[d]
+    [n_d, w_d, H, W] (f16/f32) → (mean, std), both [seq_len, H, W] f32.  The mean is aligner_merge's,
+    bitwise; std is the population standard deviation of the frame's covering terms s·(x − shift) + t in
+    the units of the mean, 0 where fewer than two terms cover a pixel.  start_steps: as aligner_merge."""
+    nd = len(xf)
+    H, W = xf[0].shape[-2:]
+    ssv = _ones_or("aligner_merge_moments", start_steps, nd)
+    mean = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
+    std = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
+    xp = (C.c_void_p * nd)(*[x.data_ptr() for x in xf])
+    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
+    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
+    nn = (C.c_int * nd)(*[x.shape[0] for x in xf])
+    stv = (C.c_int * nd)(*list(strides))
+    wv = (C.c_int * nd)(*[x.shape[1] for x in xf])
+    mode = 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
+    check(lib.rdmi_aligner_merge_moments(nd, xp, mode, sp, tp, nn, stv, ssv, wv, seq_len, H * W, shift.data_ptr(),
+                                         mean.data_ptr(), std.data_ptr(), _stream()), "rdmi_aligner_merge_moments")
+    return mean, std
+
+
+def aligner_merge_partial_window_moments(xf: Sequence[Optional[torch.Tensor]], k0: Sequence[int], n: Sequence[int],
+                                         scales, trans, strides, w: Sequence[int], f0: int, nf: int, HW: int,
+                                         shift: torch.Tensor, x_f32, seq_len: int,
+                                         out: Optional[torch.Tensor] = None,
+                                         start_steps: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """aligner_merge_partial_window for both moments (rdmi_aligner_merge_partial_window_moments): → f64
+    [nf, 2, HW], per frame the sum of the rank's covering terms s·(x − shift) + t, then the sum of their
+    squares.  seq_len is always needed (the layout is always checked); start_steps None: all ones."""
+    nd = len(xf)
+    ssv = _ones_or("aligner_merge_partial_window_moments", start_steps, nd)
+    if out is None:
+        out = torch.empty((nf, 2, HW), dtype=torch.float64, device=shift.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (nf, 2, HW) or not out.is_contiguous():
+        raise ValueError("aligner_merge_partial_window_moments: out must be contiguous f64 [nf, 2, HW]")
+    xp = (C.c_void_p * nd)(*[(x.data_ptr() if x is not None and x.shape[0] else None) for x in xf])
+    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
+    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
+    nn = (C.c_int * nd)(*list(n))
+    kk = (C.c_int * nd)(*list(k0))
+    nl = (C.c_int * nd)(*[(x.shape[0] if x is not None else 0) for x in xf])
+    stv = (C.c_int * nd)(*list(strides))
+    wv = (C.c_int * nd)(*list(w))
+    check(lib.rdmi_aligner_merge_partial_window_moments(nd, xp, int(x_f32), sp, tp, nn, stv, ssv, kk, nl, wv,
+                                                        int(seq_len), f0, nf, HW, shift.data_ptr(), out.data_ptr(),
+                                                        _stream()), "rdmi_aligner_merge_partial_window_moments")
+    return out
+
+
+def aligner_merge_finish_pieces_moments(recv: torch.Tensor, pieces: Sequence[Tuple[int, int]], n: Sequence[int],
+                                        strides: Sequence[int], w: Sequence[int], f0: int, nf: int, HW: int,
+                                        seq_len: int, start_steps: Optional[Sequence[int]] = None
+                                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """aligner_merge_finish_pieces for both moments (rdmi_aligner_merge_finish_pieces_moments): recv f64
+    [Σ nf_q, 2, HW] → (mean, std), both f32 [nf, HW]."""
+    if recv.dtype != torch.float64:
+        raise TypeError("aligner_merge_finish_pieces_moments: f64 sums expected")
+    nd, npc = len(n), len(pieces)
+    ssv = _ones_or("aligner_merge_finish_pieces_moments", start_steps, nd)
+    mean = torch.empty((nf, HW), dtype=F32, device=recv.device)
+    std = torch.empty((nf, HW), dtype=F32, device=recv.device)
+    nn = (C.c_int * nd)(*list(n))
+    stv = (C.c_int * nd)(*list(strides))
+    wv = (C.c_int * nd)(*list(w))
+    pf = (C.c_int * max(npc, 1))(*[p[0] for p in pieces])
+    pn = (C.c_int * max(npc, 1))(*[p[1] for p in pieces])
+    check(lib.rdmi_aligner_merge_finish_pieces_moments(nd, nn, stv, ssv, wv, int(seq_len), f0, nf, HW, npc, pf, pn,
+                                                       recv.data_ptr() if recv.numel() else None,
+                                                       mean.data_ptr() if nf else None,
+                                                       std.data_ptr() if nf else None, _stream()),
+          "rdmi_aligner_merge_finish_pieces_moments")
+    return mean, std
+
+
+def scale_spread_(x: torch.Tensor, mm: torch.Tensor) -> torch.Tensor:
+    """In place x ← (x / (max − min)) · 2 with [min, max] = mm on the device: renormalize_ without its
+    offsets, which takes a spread from the merged map's units to those of the renormalised map."""
+    _need(x, F32, "scale_spread.x")
+    check(lib.rdmi_scale_spread_f32(x.data_ptr(), x.numel(), mm.data_ptr(), _stream()), "rdmi_scale_spread")
+    return x
+
+
 # ----------------------------------------------------------------------------- frame ingest / resize
 _RESIZE_MODES = {"NEAREST": _N.RDMI_RESIZE_NEAREST, "BILINEAR": _N.RDMI_RESIZE_BILINEAR,
                  "BICUBIC": _N.RDMI_RESIZE_BICUBIC}

@@ -46,7 +46,13 @@ class RollingDepthOutput:
     (rollingimg_pipeline.py:424-433) and reads R_pred / G_pred / B_pred / aligned_snippet_pred_ls;
     for the depth pipeline those are filled (by __call__ only) as a compatibility decision
     (SURVEY.md §8b): R = G = B = depth·0.5 + 0.5 ([N,1,H,W] in [0,1], what run_video multiplies by
-    255) and aligned_snippet_pred_ls = [the co-aligned depth repeated to 3 channels]."""
+    255) and aligned_snippet_pred_ls = [the co-aligned depth repeated to 3 channels].
+
+    depth_uncertainty (the build's own, forward(output_uncertainty=True); None otherwise): [N, 1, H, W]
+    f32 — per pixel the population standard deviation of the co-aligned snippet predictions whose mean is
+    depth_coaligned, in depth_coaligned's units (its range is [-1, 1]); 0 where fewer than two snippets
+    cover a frame.  f32 on the host: f16 would flush small spreads.  With refine_step > 0 it still
+    describes the co-aligned stage, not the refined depth_pred."""
     input_rgb: torch.Tensor
     depth_pred: torch.Tensor
     snippet_ls: Optional[List[torch.Tensor]]
@@ -55,6 +61,7 @@ class RollingDepthOutput:
     G_pred: Optional[torch.Tensor] = None
     B_pred: Optional[torch.Tensor] = None
     aligned_snippet_pred_ls: Optional[List[torch.Tensor]] = None
+    depth_uncertainty: Optional[torch.Tensor] = None
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -167,6 +174,13 @@ def check_refine_stride(refine_stride, refine_snippet_len: int) -> int:
         raise ValueError(f"refine_stride must be an int in 1 .. refine_snippet_len ({refine_snippet_len}), "
                          f"got {refine_stride!r}")
     return int(s)
+
+
+def check_output_uncertainty(output_uncertainty) -> bool:
+    """`output_uncertainty` must be a bool (TypeError otherwise: a truthy tensor or count is a mistake)."""
+    if not isinstance(output_uncertainty, bool):
+        raise TypeError(f"output_uncertainty must be a bool, got {type(output_uncertainty).__name__}")
+    return output_uncertainty
 
 
 class RollingDepthPipeline:
@@ -564,14 +578,16 @@ class RollingDepthPipeline:
                  refine_start_dilation: int = 6, generator: Union[torch.Generator, None] = None,
                  verbose: bool = False, max_vae_bs: int = 4, unload_snippet: bool = False,
                  restore_res: bool = False, input_fg_video_path=None, refine_stride: int = 1,
-                 **kw) -> RollingDepthOutput:
+                 output_uncertainty: bool = False, **kw) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:78-176.  `input_video_path` (or the fork's `input_fg_video_path`):
         a video file (decoding needs PyAV, absent from this image), decoded uint8 rgb24 frames
         [N, H, W, 3] (numpy / torch: resized to processing_res and normalised on the device,
         video_io.load_video_frames), or an already-normalised float [N, 3, H, W] tensor in [-1, 1]
         (used as is: processing_res and restore_res do not apply to it).  `refine_stride` (the build's own,
-        1 … refine_snippet_len): see forward()."""
+        1 … refine_snippet_len) and `output_uncertainty`: see forward().  restore_res resizes
+        depth_uncertainty as it resizes depth_pred."""
         check_refine_stride(refine_stride, refine_snippet_len)
+        check_output_uncertainty(output_uncertainty)
         assert processing_res >= 0
         if processing_res > 1024:
             logging.warning(f"Procssing at high-resolution ({processing_res}) may lead to suboptimal accuracy.")
@@ -594,9 +610,9 @@ class RollingDepthPipeline:
         out = self.forward(frames[None] if frames.dim() == 4 else frames, dilations, cap_dilation, snippet_lengths,
                            init_infer_steps, strides, coalign_kwargs, refine_step, refine_snippet_len,
                            refine_start_dilation, generator, verbose, max_vae_bs, unload_snippet,
-                           refine_stride=refine_stride, **kw)
+                           refine_stride=refine_stride, output_uncertainty=output_uncertainty, **kw)
         if restore_res:  # rollingdepth_pipeline.py:155-173 (torchvision resize, antialias=True), on the device
-            for name in ("input_rgb", "depth_pred"):
+            for name in ("input_rgb", "depth_pred") + (("depth_uncertainty",) if output_uncertainty else ()):
                 t = getattr(out, name)
                 r = K.resize(t.to(self.device, torch.float32), original_res, resample_method.upper())
                 setattr(out, name, r.to(t.dtype).cpu())
@@ -608,7 +624,7 @@ class RollingDepthPipeline:
 
     def _forward_sharded(self, input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs, refine_step,
                          refine_snippet_len, refine_start_dilation, init_noise, record, generator=None, strides=1,
-                         refine_stride: int = 1):
+                         refine_stride: int = 1, output_uncertainty: bool = False):
         """forward() over W ranks (shard.sharded_forward), outputs assembled on every rank.  Dilations
         arrive already capped and strides validated (forward's checks ran); the snippets are all-gathered
         at full resolution only here, to honour the snippet_ls contract (bench.py keeps them distributed)."""
@@ -622,7 +638,7 @@ class RollingDepthPipeline:
                              gather=True, record=record, generator=generator,
                              init_infer_steps=list(init_infer_steps),
                              strides=list(strides) if isinstance(strides, (list, tuple)) else strides,
-                             refine_stride=refine_stride)
+                             refine_stride=refine_stride, output_uncertainty=output_uncertainty)
         snips = gather_rows_by_dilation([r.to(self.dtype) for r in so.snippet_rows], so.snippet_counts, world,
                                         self._group)
         H, W = so.depth_pred_full.shape[-2:]
@@ -630,9 +646,10 @@ class RollingDepthPipeline:
         snip_host = [self._to_host_async(s.view(s.shape[0], s.shape[1], 1, H, W), d2h) for s in snips]
         rgb = input_frames[0].to(self.device, self.dtype) / 2.0 + 0.5
         outs = [self._to_host_async(t, d2h) for t in (rgb, so.depth_pred_full, so.depth_coaligned_full)]
+        unc = self._to_host_async(so.depth_uncertainty_full, d2h) if output_uncertainty else None
         d2h.synchronize()
         return RollingDepthOutput(input_rgb=outs[0], depth_pred=outs[1], snippet_ls=snip_host,
-                                  depth_coaligned=outs[2])
+                                  depth_coaligned=outs[2], depth_uncertainty=unc)
 
     @torch.no_grad()
     def forward(self, input_frames: torch.Tensor, dilations: List[int], cap_dilation: bool,
@@ -640,12 +657,18 @@ class RollingDepthPipeline:
                 coalign_kwargs: Union[Dict, None], refine_step: int, refine_snippet_len: int,
                 refine_start_dilation: int, generator: Union[torch.Generator, None], verbose: bool,
                 max_vae_bs: int, unload_snippet: bool, init_noise: Optional[torch.Tensor] = None,
-                record: Optional[dict] = None, refine_stride: int = 1) -> RollingDepthOutput:
+                record: Optional[dict] = None, refine_stride: int = 1,
+                output_uncertainty: bool = False) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:193-353.  `refine_stride` (the build's own, 1 … refine_snippet_len):
         each refine step starts its snippets that many positions apart inside every residue class mod the
         step's dilation (refine_snippet_indice), so a frame passes the UNet about refine_snippet_len /
-        refine_stride times per step instead of refine_snippet_len times; 1 is the reference's refine."""
+        refine_stride times per step instead of refine_snippet_len times; 1 is the reference's refine.
+        `output_uncertainty` (the build's own): also return RollingDepthOutput.depth_uncertainty, the
+        per-pixel spread of the co-aligned snippets around depth_coaligned (one fused merge kernel in place
+        of the merge; every other output is bitwise unchanged).  With refine_step > 0 it still describes
+        the co-aligned stage."""
         refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
+        check_output_uncertainty(output_uncertainty)
         # ----------------- checks (rollingdepth_pipeline.py:214-252)
         assert 1 in dilations, "dilations should include 1"
         assert len(snippet_lengths) == len(set(snippet_lengths)), f"Repeated values found in {snippet_lengths = }"
@@ -697,7 +720,7 @@ class RollingDepthPipeline:
             if dist.get_world_size(self._group) > 1:
                 return self._forward_sharded(input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs,
                                              refine_step, refine_snippet_len, refine_start_dilation, init_noise,
-                                             record, generator, strides, refine_stride)
+                                             record, generator, strides, refine_stride, output_uncertainty)
         # ----------------- encode (H2D boundary :263)
         frames = input_frames[0].to(self.device)
         # input_rgb = frames / 2 + 0.5 in f16 as the reference computes it on the host (x/2 is exact,
@@ -719,11 +742,15 @@ class RollingDepthPipeline:
                      for s in snippets]
         # ----------------- co-alignment + renormalisation (:306-318)
         aligner = DepthAligner(device=self.device, verbose=verbose, **(coalign_kwargs or {}))
-        merged, scales, trans, hist = aligner.run([s.view(s.shape[0], s.shape[1], 1, H, W) for s in snippets],
-                                                  dilations, strides=strides if strided else None,
-                                                  sequence_length=N if strided else None, merged_f32=self.merge_f32)
+        merged, scales, trans, hist, *spread = aligner.run(
+            [s.view(s.shape[0], s.shape[1], 1, H, W) for s in snippets], dilations,
+            strides=strides if strided else None, sequence_length=N if strided else None, merged_f32=self.merge_f32,
+            uncertainty=output_uncertainty)
         d = merged.float().contiguous()
-        K.renormalize_(d, K.minmax(d))
+        mm = K.minmax(d)
+        K.renormalize_(d, mm)
+        if output_uncertainty:  # the spread in the renormalised map's units (mm: the merged map's min / max)
+            spread = K.scale_spread_(spread[0].contiguous(), mm)
         coaligned = d.to(self.dtype)
         _progress("co-alignment done")
         if record is not None:
@@ -744,6 +771,7 @@ class RollingDepthPipeline:
             depth = coaligned
         # ----------------- outputs (:345-353, D2H boundary; pinned, async, one sync)
         outs = [self._to_host_async(t, d2h) for t in (depth, coaligned)]
+        unc = self._to_host_async(spread, d2h) if output_uncertainty else None
         d2h.synchronize()
         return RollingDepthOutput(input_rgb=rgb_host, depth_pred=outs[0], snippet_ls=snip_host,
-                                  depth_coaligned=outs[1])
+                                  depth_coaligned=outs[1], depth_uncertainty=unc)

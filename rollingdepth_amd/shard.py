@@ -271,19 +271,35 @@ def merge_exchange_plan(counts: Sequence[int], strides: Sequence[int], w: Sequen
 
 
 def _merge_windowed(rows, k0, counts, scales, trans, strides, slens, N: int, HW: int, shift, x_f32, group,
-                    start_steps: Optional[Sequence[int]] = None):
+                    start_steps: Optional[Sequence[int]] = None, moments: bool = False):
     """merge_scaled_triplets over W ranks: per-rank f64 sums of only the frames its snippets cover, an
     all-to-all of the rows each rank's frame chunk needs (uneven row counts; RCCL over xGMI), then
     the received pieces added per frame in source-rank order and ÷ the cover count (f64 sums: the
     single-GPU merge bitwise).  Returns this rank's chunk
     [f1 − f0, HW] f32.  Moves each rank's covered frames instead of N·HW·8 B per rank.
-    start_steps (None or all ones: the start-step-1 calls): frames between snippet starts per dilation."""
+    start_steps (None or all ones: the start-step-1 calls): frames between snippet starts per dilation.
+    moments=True: the same plan over f64 rows [2, HW] per frame (Σ then Σ of squares of the terms: twice
+    the bytes, a frame still one row of the all-to-all) through the _moments calls → (mean chunk, std
+    chunk), both [f1 − f0, HW] f32; the mean as above, the std the spread of the frame's covering terms."""
     from . import kernels as K
 
     world, rank = _world(group), _rank(group)
     ss = dict(start_steps=list(start_steps), seq_len=N) if _strided(start_steps) else {}
     ranges, send, recv = merge_exchange_plan(counts, strides, slens, N, world, rank, start_steps)
     f0, f1 = chunk_bounds(N, world)[rank]
+    if moments:
+        steps = list(start_steps) if start_steps is not None else None
+        sums = torch.empty((sum(b - a for a, b in ranges), 2, HW), dtype=torch.float64, device=shift.device)
+        o = 0
+        for a, b in ranges:
+            K.aligner_merge_partial_window_moments([r if r.shape[0] else None for r in rows], k0, counts, scales,
+                                                   trans, strides, slens, a, b - a, HW, shift, x_f32, N,
+                                                   out=sums[o:o + b - a], start_steps=steps)
+            o += b - a
+        rbuf = exchange_window_rows(sums, send, [sum(m for _, m in pc) for pc in recv], group)
+        pieces = [pc for src in recv for pc in src]
+        return K.aligner_merge_finish_pieces_moments(rbuf, pieces, counts, strides, slens, f0, f1 - f0, HW, N,
+                                                     start_steps=steps)
     sums = torch.empty((sum(b - a for a, b in ranges), HW), dtype=torch.float64, device=shift.device)
     o = 0
     for a, b in ranges:
@@ -333,7 +349,8 @@ def _mark(timing: Optional[list], name: str):
 class ShardedOutput:
     """Distributed RollingDepthOutput: this rank's frame chunk [f0, f1) of depth_pred /
     depth_coaligned / input_rgb, its own decoded snippets (snippet_rows[d] are global snippets
-    snippet_k0[d] ..), and — when gathered — the full maps."""
+    snippet_k0[d] ..), and — when gathered — the full maps.  With output_uncertainty also depth_uncertainty
+    (this rank's chunk, f32) and, gathered, depth_uncertainty_full."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -347,7 +364,8 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
                     refine_start_dilation: int = 6, gather: bool = False, record: Optional[dict] = None,
                     generator: Optional[torch.Generator] = None,
                     init_infer_steps: Union[int, Sequence[int]] = 1, timing: Optional[list] = None,
-                    strides: Union[int, Sequence[int]] = 1, refine_stride: int = 1) -> ShardedOutput:
+                    strides: Union[int, Sequence[int]] = 1, refine_stride: int = 1,
+                    output_uncertainty: bool = False) -> ShardedOutput:
     """Multi-GPU RollingDepthPipeline.forward (every preset: refine_step > 0 included).
 
     `input_frames` is either the whole video [1,N,3,H,W] / [N,3,H,W], or — with `num_frames=N` —
@@ -365,12 +383,17 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     get_snippet_indice's `stride`; called start steps below), one int >= 1 or one per dilation; the
     dilations' snippets together must reach every frame (ValueError before any inference, as forward()).
     `refine_stride`: forward()'s (1 … refine_snippet_len): each rank takes its contiguous range of the
-    step's shorter class-major list (pipeline.refine_snippet_indice)."""
+    step's shorter class-major list (pipeline.refine_snippet_indice).
+    `output_uncertainty`: forward()'s — the windowed merge carries both moments and the output gains
+    depth_uncertainty, this rank's chunk [f1 − f0, 1, H, W] f32 of the co-aligned snippets' per-pixel spread
+    in depth_coaligned's units (scaled with the all-reduced min / max), and depth_uncertainty_full under
+    `gather`; to_host copies it as the other maps."""
     from . import kernels as K
     from .aligner import DepthAligner, check_row_layout, snippet_count, snippet_last, snippet_start
-    from .pipeline import check_refine_stride
+    from .pipeline import check_output_uncertainty, check_refine_stride
 
     refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
+    check_output_uncertainty(output_uncertainty)
 
     if group is None:
         group = dist.group.WORLD
@@ -464,13 +487,20 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     _mark(timing, "aligner")
     merged = _merge_windowed(rows, k0, counts, scales, trans, frame_steps, slens, N, H * W, shift,
                              1 if rows_f32 else (2 if pipe.merge_f32 else 0), group,
-                             start_steps if strided else None)
+                             start_steps if strided else None, moments=output_uncertainty)
+    spread = None
+    if output_uncertainty:
+        merged, spread = merged
     # merge_scaled_triplets returns the snippets' dtype (unless the pipeline merges in f32)
     d = (merged if (pipe.merge_f32 or rows_f32) else merged.to(pipe.dtype).float()).contiguous()
     mm_d = K.minmax(d) if d.numel() else torch.tensor([float("inf"), float("-inf")], device=dev)
     gmm = _all_reduce_minmax(mm_d, group)
     if d.numel():
         K.renormalize_(d, gmm)
+    if output_uncertainty:
+        if spread.numel():
+            K.scale_spread_(spread, gmm)
+        spread = spread.view(f1 - f0, 1, H, W)
     coaligned = d.to(pipe.dtype).view(f1 - f0, 1, H, W)
     del ws
     _mark(timing, "merge")
@@ -500,12 +530,18 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
                       loss_history=hist)
     out = ShardedOutput(frame_range=(f0, f1), depth_pred=depth, depth_coaligned=coaligned, snippet_rows=rows,
                         snippet_k0=k0, snippet_counts=counts, dilations=dil, input_rgb=None, snippet_host=snip_host)
+    if output_uncertainty:
+        out.depth_uncertainty = spread
     if gather:
         out.depth_pred_full = _all_gather_rows(depth, N, world, group)
         out.depth_coaligned_full = _all_gather_rows(coaligned, N, world, group)
+        if output_uncertainty:
+            out.depth_uncertainty_full = _all_gather_rows(spread, N, world, group)
     if to_host:
         out.depth_pred = pipe._to_host_async(depth, d2h)
         out.depth_coaligned = pipe._to_host_async(coaligned, d2h) if refine_step > 0 else out.depth_pred
+        if output_uncertainty:
+            out.depth_uncertainty = pipe._to_host_async(spread, d2h)
         if f1 > f0:
             out.input_rgb = pipe._to_host_async(mine_frames.to(dev, pipe.dtype) / 2.0 + 0.5, d2h)
         d2h.synchronize()
