@@ -437,6 +437,42 @@ int rdmi_aligner_merge_finish_pieces_moments(int n_dil, const int* n, const int*
  * offsets: a spread of the merged map in the units of the renormalised one (since rdmi_version 6). */
 int rdmi_scale_spread_f32(float* x, long n, const float* minmax, void* stream);
 
+/* Median merge (since rdmi_version 7): the per-pixel median of a frame's covering terms in place of their
+ * mean, and optionally their median absolute deviation (MAD) as the spread.
+ *   Terms.   The covering terms of frame f and pixel p are a_1 … a_c, the f32 values rdmi_aligner_merge_moments
+ *            forms in each x_f32 mode (0 / 1 / 2).  The coverage rule, the start steps and the layout checks
+ *            before any launch are those of rdmi_aligner_merge_moments; Σ w_d ≤ 64, so c ≤ 64.
+ *   Median.  The terms sorted ascending.  c odd: the middle term.  c even:
+ *            (float)(((double)lo + (double)hi) * 0.5) of the two middle terms.  c = 0: 0.
+ *   MAD.     d_i = fabsf(a_i − med), one f32 subtraction; MAD is the median of the d_i by the same rule, 0 for
+ *            c ≤ 1.  It is the raw MAD: no 1.4826 factor is applied.
+ *   Inputs are finite: NaN and the sign of a zero are not part of the contract.  The result depends only on
+ *   the multiset of terms, never on their order.
+ * rdmi_aligner_merge_median: the fused single-GPU form, one pass over the snippets → med_out [seq_len][HW]
+ * f32 and, unless NULL, mad_out [seq_len][HW] f32.  With HW % 4 == 0, every base pointer 16-byte aligned and
+ * at most 16 terms on any frame a lane takes 4 consecutive pixels, otherwise one.  A null med_out → RDMI_E_ARG.
+ * Sharded form.  rdmi_aligner_merge_partial_window_terms writes the covering terms of this rank's snippets
+ * (k0 / nloc as rdmi_aligner_merge_partial_window_moments) unreduced: those of frame f0 + i go to rows
+ * row_off[i] … row_off[i + 1] − 1 of terms_out [rows][HW] f32 in the merge's (d ascending, j descending)
+ * order.  row_off [nf + 1] lives on the device; the library recounts the rows on the host from the index map
+ * and returns RDMI_E_ARG when `rows` differs; the kernel never writes more than row_off[i + 1] − row_off[i] rows
+ * for a frame, nor beyond `rows`.  rows = 0 launches nothing.
+ * rdmi_aligner_median_rows: frame i selects over rows row_idx[frame_off[i] … frame_off[i + 1]) of `rows`
+ * [n_rows][HW] f32 (frame_off [nf + 1] and row_idx on the device) → med_out [nf][HW] and, unless NULL, mad_out.
+ * The count is clamped to max_count (1 … 64, else RDMI_E_ARG), indices outside [0, n_rows) are skipped, a
+ * frame with no rows gives 0; nf < 0 → RDMI_E_ARG; nf = 0 launches nothing and needs no outputs. */
+int rdmi_aligner_merge_median(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                              const float* const* t, const int* n, const int* stride, const int* start_step,
+                              const int* w, int seq_len, long HW, const float* shift, float* med_out,
+                              float* mad_out, void* stream);
+int rdmi_aligner_merge_partial_window_terms(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                                            const float* const* t, const int* n, const int* stride,
+                                            const int* start_step, const int* k0, const int* nloc, const int* w,
+                                            int seq_len, int f0, int nf, long HW, const float* shift,
+                                            const int* row_off, long rows, float* terms_out, void* stream);
+int rdmi_aligner_median_rows(const float* rows, long n_rows, const int* frame_off, const int* row_idx, int nf,
+                             long HW, int max_count, float* med_out, float* mad_out, void* stream);
+
 /* Single-head flash attention for head dim 512 (f16): the VAE mid-block attention
  * (unet_2d_blocks.py:680-697 through AttnProcessor2_0's 4-D path, attention_processor.py:2172-2276 —
  * one head, d = C = 512) as one pass over K / Vᵀ instead of f32 scores → softmax → PV.

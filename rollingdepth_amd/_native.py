@@ -131,6 +131,13 @@ _SIGS = {
                                                        C.POINTER(i32), i32, i32, i32, i64, i32, C.POINTER(i32),
                                                        C.POINTER(i32), vp, vp, vp, vp]),
     "rdmi_scale_spread_f32": (i32, [vp, i64, vp, vp]),
+    "rdmi_aligner_merge_median": (i32, [i32, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32),
+                                        C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i64, vp, vp, vp, vp]),
+    "rdmi_aligner_merge_partial_window_terms": (i32, [i32, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp),
+                                                      C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                                      C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32, i32,
+                                                      i64, vp, vp, i64, vp, vp]),
+    "rdmi_aligner_median_rows": (i32, [vp, i64, vp, vp, i32, i64, i32, vp, vp, vp]),
     "rdmi_depth_metrics_workspace": (i64, [i32, i64]),
     "rdmi_depth_moments": (i32, [vp, i32, vp, i32, vp, i32, i64, f32, f32, vp, vp]),
     "rdmi_depth_fit": (i32, [vp, i32, i64, i32, vp, vp, vp]),

@@ -105,7 +105,8 @@ class DepthAligner:
         return scales, trans, hist, ws
 
     def run(self, snippet_ls: List[torch.Tensor], dilations: List[int], strides: Optional[List[int]] = None,
-            sequence_length: Optional[int] = None, merged_f32: bool = False, uncertainty: bool = False):
+            sequence_length: Optional[int] = None, merged_f32: bool = False, uncertainty: bool = False,
+            merge: str = "mean"):
         """depth_aligner.py:68-120.  merged_f32=True (the pipeline's internal use): the merge of f16
         snippets runs in f32 arithmetic and is returned in f32, without the reference's f16 roundings
         of s·x+t and of the merged map (RollingDepthPipeline.merge_f32).
@@ -123,9 +124,17 @@ class DepthAligner:
         (kernels.aligner_merge_moments in place of aligner_merge, same merged map bitwise) and a fifth
         element is returned: the per-pixel population standard deviation of a frame's covering terms
         s·(x − min) + t, [N, 1, H, W] f32 in the units of the merged map before any renormalisation, 0
-        where fewer than two snippets cover a frame."""
+        where fewer than two snippets cover a frame.
+
+        merge="median" (the build's own; "mean" | "median", anything else is a ValueError): the merged map is
+        the per-pixel median of a frame's covering terms instead of their mean (kernels.aligner_merge_median;
+        the mean of the two middle terms for an even count), and the fifth element under uncertainty=True is
+        their median absolute deviation around it — the raw MAD, no 1.4826 factor.  Scales, translations and
+        the loss history are the same."""
         if not isinstance(uncertainty, bool):
             raise TypeError(f"uncertainty must be a bool, got {type(uncertainty).__name__}")
+        if not isinstance(merge, str) or merge not in ("mean", "median"):
+            raise ValueError(f'merge must be "mean" or "median", got {merge!r}')
         dev = torch.device(self.device)
         snippet_ls = [s.to(dev) for s in snippet_ls]
         lengths = [s.shape[1] for s in snippet_ls]
@@ -156,7 +165,12 @@ class DepthAligner:
         frame_steps = [g + 1 for g in gaps]
         scales, trans, hist, ws = self.optimize_prepared(xs, frame_steps, seq_len, start_steps)
         spread = None
-        if uncertainty:
+        if merge == "median":
+            merged = K.aligner_merge_median(flat, scales, trans, frame_steps, seq_len, shift, f32_arith=merged_f32,
+                                            start_steps=start_steps, mad=uncertainty)
+            if uncertainty:
+                merged, spread = merged
+        elif uncertainty:
             merged, spread = K.aligner_merge_moments(flat, scales, trans, frame_steps, seq_len, shift,
                                                      f32_arith=merged_f32, start_steps=start_steps)
         else:

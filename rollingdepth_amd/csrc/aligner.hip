@@ -17,6 +17,8 @@
 //                s·x+t, rounded through the snippet dtype where the reference computes in it.
 // merge_moments — the same mean plus the per-pixel standard deviation of those slots' terms, in one pass
 //                (the build's own; end of this file).
+// merge_median — the per-pixel median of those slots' terms in place of their mean, optionally with their
+//                median absolute deviation (the build's own; end of this file).
 //
 // Snippet lengths may differ per dilation (rollingdepth_pipeline.py:221-226).  The reference then
 // scatters dilation i's slot j into row i·w_i + j of its [Σw, N, P] tensors M / M_depth / B
@@ -35,6 +37,8 @@
 // The sharded merge takes start steps through its _strided entry points (window sums: merge_k<true>;
 // cover count: rdmi_cover_count).
 #pragma clang fp contract(off)
+#include <utility>
+
 #include "common.h"
 #include "aligner_index.h"
 #include "aligner_ws.h"
@@ -1155,17 +1159,17 @@ int moments_start_steps(const char* what, int nd, const int* start_step, const i
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int moments_launch(const char* what, int n_dil, const void* const* xf, int x_f32, const float* const* s,
-                   const float* const* t, const int* n, const int* stride, const int* start_step, const int* k0,
-                   const int* nloc, const int* w, int seq_len, int f0, int nf, long HW, const float* shift,
-                   float* mean_out, float* std_out, double* mom_out, void* stream) {
+// The argument and layout checks every moments / median call makes before any launch, and the job they fill
+// (outputs are the caller's to set).
+int moments_fill(const char* what, int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                 const float* const* t, const int* n, const int* stride, const int* start_step, const int* k0,
+                 const int* nloc, const int* w, int seq_len, int f0, int nf, long HW, const float* shift, MergeP& p,
+                 bool* strided) {
   RDMI_REQUIRE(n_dil >= 1 && n_dil <= MAXD && xf && s && t && n && stride && start_step && w && HW > 0 &&
                    seq_len > 0 && x_f32 >= 0 && x_f32 <= 2,
                RDMI_E_ARG, "%s: bad args", what);
   RDMI_REQUIRE(f0 >= 0 && nf >= 0 && f0 <= seq_len && nf <= seq_len - f0, RDMI_E_ARG,
                "%s: frames %d+%d outside the %d of the sequence", what, f0, nf, seq_len);
-  MomP pp{};
-  MergeP& p = pp.m;
   int rows = 0;
   for (int d = 0; d < n_dil; ++d) {
     const int kk = k0 ? k0[d] : 0, nl = nloc ? nloc[d] : n[d];
@@ -1182,12 +1186,23 @@ int moments_launch(const char* what, int n_dil, const void* const* xf, int x_f32
     rows += w[d];
   }
   RDMI_REQUIRE(rows <= MAXR, RDMI_E_UNSUPPORTED, "%s: snippet lengths sum to %d (at most %d)", what, rows, MAXR);
-  p.nd = n_dil; p.xf32 = x_f32; p.HW = HW; p.shift = shift; p.out = mean_out; p.f0 = f0;
+  p.nd = n_dil; p.xf32 = x_f32; p.HW = HW; p.shift = shift; p.f0 = f0;
+  return moments_start_steps(what, n_dil, start_step, p.n, p.stride, p.w, seq_len, p.ss, p.last, strided);
+}
+
+int moments_launch(const char* what, int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                   const float* const* t, const int* n, const int* stride, const int* start_step, const int* k0,
+                   const int* nloc, const int* w, int seq_len, int f0, int nf, long HW, const float* shift,
+                   float* mean_out, float* std_out, double* mom_out, void* stream) {
+  MomP pp{};
+  MergeP& p = pp.m;
+  bool strided = false;
+  if (int rc = moments_fill(what, n_dil, xf, x_f32, s, t, n, stride, start_step, k0, nloc, w, seq_len, f0, nf, HW,
+                            shift, p, &strided))
+    return rc;
+  p.out = mean_out;
   pp.std_out = std_out;
   pp.mom = mom_out;
-  bool strided = false;
-  if (int rc = moments_start_steps(what, n_dil, start_step, p.n, p.stride, p.w, seq_len, p.ss, p.last, &strided))
-    return rc;
   if (nf == 0) return 0;
   bool vec = HW % 4 == 0 && aligned16(mean_out) && aligned16(std_out) && aligned16(mom_out);
   for (int d = 0; d < n_dil; ++d) vec = vec && (p.nloc[d] == 0 || aligned16(p.x[d]));
@@ -1301,4 +1316,383 @@ extern "C" int rdmi_aligner_merge_finish_pieces_moments(int n_dil, const int* n,
     fs = fe;
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Median merge (since rdmi_version 7): per pixel the median of a frame's covering terms — the f32 values
+// mom_term forms, the ones merge_k averages — and optionally their median absolute deviation.
+//   median: the terms sorted ascending; c odd: the middle one; c even: (float)(((double)lo + (double)hi) · 0.5)
+//           of the two middle ones; c = 0: 0.
+//   MAD:    d_i = fabsf(a_i − median), one f32 subtraction; the median of the d_i by the same rule (raw: no
+//           1.4826 factor); 0 for c ≤ 1.
+// Inputs are finite; NaN and the sign of a zero are not part of the contract.  The result depends only on the
+// multiset of terms: the sharded form may hand them over in any order.
+//
+// c is uniform per block.  A lane holds its pixel's terms in registers, padded to the kernel's capacity CAP
+// (8 / 16 / 32 / 64, picked per launch from the layout's largest cover count) with ⌊(CAP − c)/2⌋ values of −inf
+// and the rest +inf, so that after a Batcher odd-even merge sort — a fixed compare-exchange network, every
+// index a compile-time constant, v_min_f32 / v_max_f32 — the two middle terms sit at CAP/2 − 1 and CAP/2
+// whatever c is.  The deviations are formed from the sorted array (the same multiset), the −inf pads put back,
+// and the network run again.  CAP ≤ 16 takes 4 pixels per lane on the vector path of merge_moments_k, the
+// larger capacities one pixel per lane.
+namespace {
+
+struct MedNet {
+  int n;
+  unsigned char lo[544], hi[544];
+};
+
+// Batcher's odd-even merge sort for cap = 2^k inputs as a list of compare-exchanges (19 / 63 / 191 / 543 for
+// 8 / 16 / 32 / 64)
+constexpr MedNet med_net(int cap) {
+  MedNet r{};
+  for (int p = 1; p < cap; p *= 2)
+    for (int k = p; k >= 1; k /= 2)
+      for (int j = k % p; j <= cap - 1 - k; j += 2 * k)
+        for (int i = 0; i < k && i + j + k < cap; ++i)
+          if ((i + j) / (p * 2) == (i + j + k) / (p * 2)) {
+            r.lo[r.n] = (unsigned char)(i + j);
+            r.hi[r.n] = (unsigned char)(i + j + k);
+            ++r.n;
+          }
+  return r;
+}
+
+// the 0-1 principle: a network that sorts every 0/1 input sorts every input
+constexpr bool med_net_sorts01(int cap) {
+  const MedNet net = med_net(cap);
+  for (unsigned m = 0; m < (1u << cap); ++m) {
+    unsigned v = m;
+    for (int i = 0; i < net.n; ++i) {
+      const unsigned a = (v >> net.lo[i]) & 1u, b = (v >> net.hi[i]) & 1u;
+      if (a > b) v ^= (1u << net.lo[i]) | (1u << net.hi[i]);
+    }
+    for (int i = 0; i + 1 < cap; ++i)
+      if (((v >> i) & 1u) > ((v >> (i + 1)) & 1u)) return false;
+  }
+  return true;
+}
+
+template <int CAP>
+struct MedNetOf {
+  static constexpr MedNet net = med_net(CAP);
+};
+static_assert(MedNetOf<8>::net.n == 19 && MedNetOf<16>::net.n == 63 && MedNetOf<32>::net.n == 191 &&
+                  MedNetOf<64>::net.n == 543,
+              "Batcher's odd-even merge sort");
+static_assert(med_net_sorts01(8), "the 8-input network sorts");
+
+template <int CAP, int V, int K>
+__device__ __forceinline__ void med_cmpex(float (&a)[CAP][V]) {
+  constexpr int lo = MedNetOf<CAP>::net.lo[K], hi = MedNetOf<CAP>::net.hi[K];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const float x = a[lo][v], y = a[hi][v];
+    a[lo][v] = __builtin_fminf(x, y);
+    a[hi][v] = __builtin_fmaxf(x, y);
+  }
+}
+
+template <int CAP, int V, int K0, int... K>
+__device__ __forceinline__ void med_sort_part(float (&a)[CAP][V], std::integer_sequence<int, K...>) {
+  (med_cmpex<CAP, V, K0 + K>(a), ...);
+}
+
+// a[0 .. CAP) ascending, per pixel column; the list is applied 64 compare-exchanges at a time
+template <int CAP, int V, int K0 = 0>
+__device__ __forceinline__ void med_sort(float (&a)[CAP][V]) {
+  constexpr int n = MedNetOf<CAP>::net.n, m = n - K0 < 64 ? n - K0 : 64;
+  med_sort_part<CAP, V, K0>(a, std::make_integer_sequence<int, m>{});
+  if constexpr (K0 + m < n) med_sort<CAP, V, K0 + m>(a);
+}
+
+// the median of c values sorted into a padded array: the two middle terms are at CAP/2 − 1 and CAP/2
+template <int CAP, int V>
+__device__ __forceinline__ void med_middle(const float (&a)[CAP][V], int c, float (&m)[V]) {
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const float lo = a[CAP / 2 - 1][v], hi = a[CAP / 2][v];
+    m[v] = c == 0 ? 0.f : ((c & 1) ? lo : (float)(((double)lo + (double)hi) * 0.5));
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void med_store(float* o, const float (&m)[V]) {
+  if constexpr (V == 4)
+    *(f32x4*)o = f32x4{m[0], m[1], m[2], m[3]};
+  else
+    o[0] = m[0];
+}
+
+// A table entry is the same in every lane: through readfirstlane it lives in scalar registers, not in CAP × 4
+// vector registers for the whole pixel loop.
+__device__ __forceinline__ const char* med_uniform(const char* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (const char*)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ float med_uniform(float x) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
+}
+
+// One frame's pixels: tab[0 .. c) are its terms' rows (RAW: the rows hold the terms themselves, f32),
+// c ≤ CAP; med / mad: the frame's output rows (mad may be null).
+template <int CAP, int V, bool XF32, bool RAW>
+__device__ __forceinline__ void median_pixels(const MomEnt* tab, int c, float sh, bool chain, long HW, float* med,
+                                              float* mad) {
+  const int nlo = (CAP - c) >> 1;
+  const float ninf = -__builtin_inff(), pinf = __builtin_inff();
+  const long groups = HW / V;  // V == 4 only when HW % 4 == 0
+  for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < groups; g += (long)gridDim.x * blockDim.x) {
+    const long px = g * V;
+    float a[CAP][V];
+#pragma unroll
+    for (int u0 = 0; u0 < CAP; u0 += MOM_U) {  // MOM_U rows' loads issued before the first is used
+#pragma unroll
+      for (int u = u0; u < u0 + MOM_U; ++u)
+        if (u < c) mom_load<V, XF32>(med_uniform(tab[u].row), px, a[u]);
+#pragma unroll
+      for (int u = u0; u < u0 + MOM_U; ++u) {
+        if (u < c) {
+          if constexpr (!RAW) {
+            const float s = med_uniform(tab[u].s), t = med_uniform(tab[u].t);
+#pragma unroll
+            for (int v = 0; v < V; ++v) a[u][v] = mom_term(a[u][v], sh, s, t, chain);
+          }
+        } else {
+          const float pad = u - c < nlo ? ninf : pinf;
+#pragma unroll
+          for (int v = 0; v < V; ++v) a[u][v] = pad;
+        }
+      }
+    }
+    med_sort<CAP, V>(a);
+    float m[V];
+    med_middle<CAP, V>(a, c, m);
+    med_store<V>(med + px, m);
+    if (mad) {
+#pragma unroll
+      for (int u = 0; u < CAP; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const float d = __builtin_fabsf(a[u][v] - m[v]);  // +inf for the pads
+          a[u][v] = u < nlo ? ninf : d;                     // the sorted array starts with the −inf pads
+        }
+      med_sort<CAP, V>(a);
+      med_middle<CAP, V>(a, c, m);
+      med_store<V>(mad + px, m);
+    }
+  }
+}
+
+struct MedP {
+  MergeP m;     // out = the median (fused form)
+  float* mad;   // fused form; NULL: none
+  int strided;  // a start step > 1: the index map of aligner_index.h
+};
+
+template <int CAP, int V, bool XF32>
+__global__ __launch_bounds__(256) void merge_median_k(MedP pp) {
+  __shared__ MomEnt tab[MAXR];
+  __shared__ int cnt_sh;
+  const MergeP& p = pp.m;
+  const int fl = blockIdx.y, f = p.f0 + fl;
+  int c = pp.strided ? moments_table<true>(p, f, tab, &cnt_sh) : moments_table<false>(p, f, tab, &cnt_sh);
+  if (c > CAP) c = CAP;  // the host picked CAP ≥ the layout's largest cover count
+  median_pixels<CAP, V, XF32, false>(tab, c, p.shift ? p.shift[0] : 0.f, p.xf32 == 0, p.HW, p.out + (long)fl * p.HW,
+                                     pp.mad ? pp.mad + (long)fl * p.HW : nullptr);
+}
+
+// Sharded form, first half: the terms of this rank's snippets, unreduced.  Frame f0 + i's go to rows
+// row_off[i] … of terms_out in the merge's order; never more than row_off[i + 1] − row_off[i] of them and
+// never past `rows`.
+template <int V, bool XF32>
+__global__ __launch_bounds__(256) void merge_terms_k(MedP pp, const int* __restrict__ row_off, long rows,
+                                                     float* __restrict__ terms_out) {
+  __shared__ MomEnt tab[MAXR];
+  __shared__ int cnt_sh;
+  const MergeP& p = pp.m;
+  const int fl = blockIdx.y, f = p.f0 + fl;
+  int c = pp.strided ? moments_table<true>(p, f, tab, &cnt_sh) : moments_table<false>(p, f, tab, &cnt_sh);
+  const long r0 = row_off[fl], room = (long)row_off[fl + 1] - r0;
+  if (r0 < 0 || room <= 0 || r0 >= rows) return;
+  if (c > room) c = (int)room;
+  if (c > rows - r0) c = (int)(rows - r0);
+  c = __builtin_amdgcn_readfirstlane(c);
+  const float sh = p.shift ? p.shift[0] : 0.f;
+  const bool chain = p.xf32 == 0;
+  const long groups = p.HW / V;
+  for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < groups; g += (long)gridDim.x * blockDim.x) {
+    const long px = g * V;
+    for (int e0 = 0; e0 < c; e0 += MOM_U) {
+      float x[MOM_U][V];
+#pragma unroll
+      for (int u = 0; u < MOM_U; ++u)
+        if (e0 + u < c) mom_load<V, XF32>(tab[e0 + u].row, px, x[u]);
+#pragma unroll
+      for (int u = 0; u < MOM_U; ++u)
+        if (e0 + u < c) {
+          const float s = tab[e0 + u].s, t = tab[e0 + u].t;
+          float a[V];
+#pragma unroll
+          for (int v = 0; v < V; ++v) a[v] = mom_term(x[u][v], sh, s, t, chain);
+          med_store<V>(terms_out + (r0 + e0 + u) * p.HW + px, a);
+        }
+    }
+  }
+}
+
+// Sharded form, second half: frame i selects over rows row_idx[frame_off[i] … frame_off[i + 1]) of `rows`
+// ([n_rows][HW] f32), at most max_count ≤ CAP of them; indices outside [0, n_rows) are skipped.
+template <int CAP, int V>
+__global__ __launch_bounds__(256) void median_rows_k(const float* __restrict__ rows, long n_rows,
+                                                     const int* __restrict__ frame_off,
+                                                     const int* __restrict__ row_idx, long HW, int max_count,
+                                                     float* med, float* mad) {
+  __shared__ MomEnt tab[MAXR];
+  __shared__ int cnt_sh;
+  const int fl = blockIdx.y;
+  if (threadIdx.x < 64) {
+    const int i = threadIdx.x;
+    const int b = frame_off[fl];
+    int n = frame_off[fl + 1] - b;
+    if (n > max_count) n = max_count;
+    if (b < 0) n = 0;
+    bool ok = false;
+    MomEnt e{nullptr, 1.f, 0.f};
+    if (i < n) {
+      const long r = row_idx[b + i];
+      if (r >= 0 && r < n_rows) {
+        ok = true;
+        e.row = (const char*)(rows + r * HW);
+      }
+    }
+    const unsigned long long mask = __ballot(ok);
+    if (ok) tab[__popcll(mask & ((1ull << i) - 1ull))] = e;
+    if (i == 0) cnt_sh = __popcll(mask);
+  }
+  __syncthreads();
+  int c = __builtin_amdgcn_readfirstlane(cnt_sh);
+  if (c > CAP) c = CAP;
+  median_pixels<CAP, V, true, true>(tab, c, 0.f, false, HW, med + (long)fl * HW, mad ? mad + (long)fl * HW : nullptr);
+}
+
+int median_capacity(int c) { return c <= 8 ? 8 : c <= 16 ? 16 : c <= 32 ? 32 : 64; }
+
+dim3 median_grid(long groups, int nf) {
+  long gx = (groups + 256 * MOM_ITER - 1) / (256 * MOM_ITER);
+  if (gx > 1024) gx = 1024;
+  return dim3((unsigned)gx, nf);
+}
+
+}  // namespace
+
+extern "C" int rdmi_aligner_merge_median(int n_dil, const void* const* xf, int x_f32, const float* const* s,
+                                         const float* const* t, const int* n, const int* stride,
+                                         const int* start_step, const int* w, int seq_len, long HW,
+                                         const float* shift, float* med_out, float* mad_out, void* stream) {
+  const char* what = "aligner_merge_median";
+  RDMI_REQUIRE(med_out, RDMI_E_ARG, "%s: null output", what);
+  MedP pp{};
+  MergeP& p = pp.m;
+  bool strided = false;
+  if (int rc = moments_fill(what, n_dil, xf, x_f32, s, t, n, stride, start_step, nullptr, nullptr, w, seq_len, 0,
+                            seq_len, HW, shift, p, &strided))
+    return rc;
+  p.out = med_out;
+  pp.mad = mad_out;
+  pp.strided = strided;
+  int cmax = 0;
+  for (int f = 0; f < seq_len; ++f) {
+    const int c = rdmi_cover_count(p.nd, p.n, p.stride, p.w, p.ss, p.last, f);
+    if (c > cmax) cmax = c;
+  }
+  const int cap = median_capacity(cmax);
+  bool vec = cap <= 16 && HW % 4 == 0 && aligned16(med_out) && aligned16(mad_out);
+  for (int d = 0; d < n_dil; ++d) vec = vec && (p.nloc[d] == 0 || aligned16(p.x[d]));
+  const dim3 grid = median_grid(vec ? HW / 4 : HW, seq_len), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+  const bool f32 = x_f32 == 1;
+#define RDMI_MED_LAUNCH(CAP_, V_, F32_) hipLaunchKernelGGL((merge_median_k<CAP_, V_, F32_>), grid, blk, 0, st, pp)
+#define RDMI_MED_PICK(CAP_, V_)               \
+  do {                                        \
+    if (f32) RDMI_MED_LAUNCH(CAP_, V_, true); \
+    else RDMI_MED_LAUNCH(CAP_, V_, false);    \
+  } while (0)
+  if (cap == 8 && vec) RDMI_MED_PICK(8, 4);
+  else if (cap == 8) RDMI_MED_PICK(8, 1);
+  else if (cap == 16 && vec) RDMI_MED_PICK(16, 4);
+  else if (cap == 16) RDMI_MED_PICK(16, 1);
+  else if (cap == 32) RDMI_MED_PICK(32, 1);
+  else RDMI_MED_PICK(64, 1);
+#undef RDMI_MED_PICK
+#undef RDMI_MED_LAUNCH
+  return rdmi::check_launch(what);
+}
+
+extern "C" int rdmi_aligner_merge_partial_window_terms(int n_dil, const void* const* xf, int x_f32,
+                                                       const float* const* s, const float* const* t, const int* n,
+                                                       const int* stride, const int* start_step, const int* k0,
+                                                       const int* nloc, const int* w, int seq_len, int f0, int nf,
+                                                       long HW, const float* shift, const int* row_off, long rows,
+                                                       float* terms_out, void* stream) {
+  const char* what = "aligner_merge_partial_window_terms";
+  RDMI_REQUIRE(k0 && nloc, RDMI_E_ARG, "%s: k0/nloc required", what);
+  MedP pp{};
+  MergeP& p = pp.m;
+  bool strided = false;
+  if (int rc = moments_fill(what, n_dil, xf, x_f32, s, t, n, stride, start_step, k0, nloc, w, seq_len, f0, nf, HW,
+                            shift, p, &strided))
+    return rc;
+  pp.strided = strided;
+  long want = 0;  // the rows this window holds, from the index map
+  for (int f = f0; f < f0 + nf; ++f)
+    for (int d = 0; d < n_dil; ++d)
+      for (int j = 0; j < p.w[d]; ++j) {
+        const int k = rdmi_snip_at(f - j * p.stride[d], p.ss[d], p.last[d], p.n[d]);
+        want += k >= p.k0[d] && k < p.k0[d] + p.nloc[d] ? 1 : 0;
+      }
+  RDMI_REQUIRE(rows == want, RDMI_E_ARG, "%s: %ld rows, but the frames %d+%d hold %ld terms of the snippets given",
+               what, rows, f0, nf, want);
+  if (nf == 0 || rows == 0) return 0;
+  RDMI_REQUIRE(row_off && terms_out, RDMI_E_ARG, "%s: null row_off / terms_out", what);
+  bool vec = HW % 4 == 0 && aligned16(terms_out);
+  for (int d = 0; d < n_dil; ++d) vec = vec && (p.nloc[d] == 0 || aligned16(p.x[d]));
+  const dim3 grid = median_grid(vec ? HW / 4 : HW, nf), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+#define RDMI_TERMS_LAUNCH(V_, F32_) \
+  hipLaunchKernelGGL((merge_terms_k<V_, F32_>), grid, blk, 0, st, pp, row_off, rows, terms_out)
+  if (vec && x_f32 == 1) RDMI_TERMS_LAUNCH(4, true);
+  else if (vec) RDMI_TERMS_LAUNCH(4, false);
+  else if (x_f32 == 1) RDMI_TERMS_LAUNCH(1, true);
+  else RDMI_TERMS_LAUNCH(1, false);
+#undef RDMI_TERMS_LAUNCH
+  return rdmi::check_launch(what);
+}
+
+extern "C" int rdmi_aligner_median_rows(const float* rows, long n_rows, const int* frame_off, const int* row_idx,
+                                        int nf, long HW, int max_count, float* med_out, float* mad_out,
+                                        void* stream) {
+  const char* what = "aligner_median_rows";
+  RDMI_REQUIRE(nf >= 0 && HW > 0 && n_rows >= 0, RDMI_E_ARG, "%s: nf %d, HW %ld, n_rows %ld", what, nf, HW, n_rows);
+  RDMI_REQUIRE(max_count >= 1 && max_count <= MAXR, RDMI_E_ARG, "%s: max_count %d (1 … %d expected)", what, max_count,
+               MAXR);
+  if (nf == 0) return 0;
+  RDMI_REQUIRE(frame_off && med_out && (n_rows == 0 || (rows && row_idx)), RDMI_E_ARG, "%s: null argument", what);
+  const int cap = median_capacity(max_count);
+  const bool vec = cap <= 16 && HW % 4 == 0 && aligned16(rows) && aligned16(med_out) && aligned16(mad_out);
+  const dim3 grid = median_grid(vec ? HW / 4 : HW, nf), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+#define RDMI_ROWS_LAUNCH(CAP_, V_)                                                                               \
+  hipLaunchKernelGGL((median_rows_k<CAP_, V_>), grid, blk, 0, st, rows, n_rows, frame_off, row_idx, HW, max_count, \
+                     med_out, mad_out)
+  if (cap == 8 && vec) RDMI_ROWS_LAUNCH(8, 4);
+  else if (cap == 8) RDMI_ROWS_LAUNCH(8, 1);
+  else if (cap == 16 && vec) RDMI_ROWS_LAUNCH(16, 4);
+  else if (cap == 16) RDMI_ROWS_LAUNCH(16, 1);
+  else if (cap == 32) RDMI_ROWS_LAUNCH(32, 1);
+  else RDMI_ROWS_LAUNCH(64, 1);
+#undef RDMI_ROWS_LAUNCH
+  return rdmi::check_launch(what);
 }

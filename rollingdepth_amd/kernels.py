@@ -1243,6 +1243,94 @@ def aligner_merge_finish_pieces_moments(recv: torch.Tensor, pieces: Sequence[Tup
     return mean, std
 
 
+def aligner_merge_median(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: int, shift: torch.Tensor,
+                         f32_arith: bool = False, start_steps: Optional[Sequence[int]] = None, mad: bool = False):
+    """aligner_merge with the per-pixel median of a frame's covering terms in place of their mean
+    (rdmi_aligner_merge_median): xf[d] [n_d, w_d, H, W] (f16/f32) → median [seq_len, H, W] f32, or with
+    mad=True (median, mad): the terms' median absolute deviation around it, in the median's units — the raw
+    MAD, no 1.4826 factor; 0 where fewer than two terms cover a pixel.  An even number of terms gives the
+    mean of the two middle ones.  start_steps: as aligner_merge."""
+    if not isinstance(mad, bool):
+        raise TypeError(f"aligner_merge_median: mad must be a bool, got {type(mad).__name__}")
+    nd = len(xf)
+    H, W = xf[0].shape[-2:]
+    ssv = _ones_or("aligner_merge_median", start_steps, nd)
+    med = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
+    dev = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device) if mad else None
+    xp = (C.c_void_p * nd)(*[x.data_ptr() for x in xf])
+    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
+    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
+    nn = (C.c_int * nd)(*[x.shape[0] for x in xf])
+    stv = (C.c_int * nd)(*list(strides))
+    wv = (C.c_int * nd)(*[x.shape[1] for x in xf])
+    mode = 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
+    check(lib.rdmi_aligner_merge_median(nd, xp, mode, sp, tp, nn, stv, ssv, wv, seq_len, H * W, shift.data_ptr(),
+                                        med.data_ptr(), dev.data_ptr() if mad else None, _stream()),
+          "rdmi_aligner_merge_median")
+    return (med, dev) if mad else med
+
+
+def aligner_merge_partial_window_terms(xf: Sequence[Optional[torch.Tensor]], k0: Sequence[int], n: Sequence[int],
+                                       scales, trans, strides, w: Sequence[int], f0: int, nf: int, HW: int,
+                                       shift: torch.Tensor, x_f32, seq_len: int, row_off: torch.Tensor,
+                                       out: torch.Tensor,
+                                       start_steps: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The covering terms s·(x − shift) + t of this rank's snippets over frames f0 .. f0+nf-1, unreduced
+    (rdmi_aligner_merge_partial_window_terms): frame f0 + i's go to rows row_off[i] … row_off[i + 1] − 1 of
+    out (f32 [rows, HW], contiguous) in the merge's order.  row_off: int32 [nf + 1] on the device; the
+    library recounts out's rows from the index map and refuses another count."""
+    nd = len(xf)
+    what = "aligner_merge_partial_window_terms"
+    ssv = _ones_or(what, start_steps, nd)
+    if out.dtype != F32 or out.dim() != 2 or out.shape[1] != HW or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be contiguous f32 [rows, HW]")
+    if row_off.dtype != torch.int32 or tuple(row_off.shape) != (nf + 1,) or not row_off.is_contiguous():
+        raise ValueError(f"{what}: row_off must be contiguous int32 [nf + 1]")
+    if row_off.device != out.device:
+        raise ValueError(f"{what}: row_off on {row_off.device}, out on {out.device}")
+    xp = (C.c_void_p * nd)(*[(x.data_ptr() if x is not None and x.shape[0] else None) for x in xf])
+    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
+    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
+    nn = (C.c_int * nd)(*list(n))
+    kk = (C.c_int * nd)(*list(k0))
+    nl = (C.c_int * nd)(*[(x.shape[0] if x is not None else 0) for x in xf])
+    stv = (C.c_int * nd)(*list(strides))
+    wv = (C.c_int * nd)(*list(w))
+    check(lib.rdmi_aligner_merge_partial_window_terms(nd, xp, int(x_f32), sp, tp, nn, stv, ssv, kk, nl, wv,
+                                                      int(seq_len), f0, nf, HW, shift.data_ptr(), row_off.data_ptr(),
+                                                      out.shape[0], out.data_ptr() if out.numel() else None,
+                                                      _stream()), "rdmi_aligner_merge_partial_window_terms")
+    return out
+
+
+def aligner_median_rows(rows: torch.Tensor, frame_off: torch.Tensor, row_idx: torch.Tensor, nf: int, max_count: int,
+                        mad: bool = False):
+    """Per frame the median over a list of rows (rdmi_aligner_median_rows): rows f32 [n_rows, HW]; frame i
+    selects over rows row_idx[frame_off[i] : frame_off[i + 1]] (int32 device tensors, frame_off [nf + 1]), at
+    most max_count (1 … 64) of them → median [nf, HW] f32, or with mad=True (median, mad) as
+    aligner_merge_median.  A frame with no rows gives 0."""
+    what = "aligner_median_rows"
+    if not isinstance(mad, bool):
+        raise TypeError(f"{what}: mad must be a bool, got {type(mad).__name__}")
+    if rows.dtype != F32 or rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError(f"{what}: rows must be contiguous f32 [n_rows, HW]")
+    for name, t in (("frame_off", frame_off), ("row_idx", row_idx)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != rows.device:
+            raise ValueError(f"{what}: {name} must be a contiguous int32 vector on {rows.device}")
+    if frame_off.shape[0] != nf + 1:
+        raise ValueError(f"{what}: frame_off holds {frame_off.shape[0]} entries for {nf} frames")
+    if not 1 <= int(max_count) <= 64:
+        raise ValueError(f"{what}: max_count {max_count} (1 … 64)")
+    HW = rows.shape[1]
+    med = torch.empty((nf, HW), dtype=F32, device=rows.device)
+    dev = torch.empty((nf, HW), dtype=F32, device=rows.device) if mad else None
+    check(lib.rdmi_aligner_median_rows(rows.data_ptr() if rows.numel() else None, rows.shape[0], frame_off.data_ptr(),
+                                       row_idx.data_ptr() if row_idx.numel() else None, nf, HW, int(max_count),
+                                       med.data_ptr() if nf else None, dev.data_ptr() if mad and nf else None,
+                                       _stream()), "rdmi_aligner_median_rows")
+    return (med, dev) if mad else med
+
+
 def scale_spread_(x: torch.Tensor, mm: torch.Tensor) -> torch.Tensor:
     """In place x ← (x / (max − min)) · 2 with [min, max] = mm on the device: renormalize_ without its
     offsets, which takes a spread from the merged map's units to those of the renormalised map."""

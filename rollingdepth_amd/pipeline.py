@@ -52,7 +52,9 @@ class RollingDepthOutput:
     f32 — per pixel the population standard deviation of the co-aligned snippet predictions whose mean is
     depth_coaligned, in depth_coaligned's units (its range is [-1, 1]); 0 where fewer than two snippets
     cover a frame.  f32 on the host: f16 would flush small spreads.  With refine_step > 0 it still
-    describes the co-aligned stage, not the refined depth_pred."""
+    describes the co-aligned stage, not the refined depth_pred.  Under forward(merge="median") depth_coaligned
+    is the per-pixel median of those predictions and depth_uncertainty their median absolute deviation around
+    it — the raw MAD, no 1.4826 factor."""
     input_rgb: torch.Tensor
     depth_pred: torch.Tensor
     snippet_ls: Optional[List[torch.Tensor]]
@@ -181,6 +183,13 @@ def check_output_uncertainty(output_uncertainty) -> bool:
     if not isinstance(output_uncertainty, bool):
         raise TypeError(f"output_uncertainty must be a bool, got {type(output_uncertainty).__name__}")
     return output_uncertainty
+
+
+def check_merge(merge) -> str:
+    """`merge` must be "mean" or "median" (ValueError otherwise, before any device work)."""
+    if not isinstance(merge, str) or merge not in ("mean", "median"):
+        raise ValueError(f'merge must be "mean" or "median", got {merge!r}')
+    return merge
 
 
 class RollingDepthPipeline:
@@ -578,16 +587,17 @@ class RollingDepthPipeline:
                  refine_start_dilation: int = 6, generator: Union[torch.Generator, None] = None,
                  verbose: bool = False, max_vae_bs: int = 4, unload_snippet: bool = False,
                  restore_res: bool = False, input_fg_video_path=None, refine_stride: int = 1,
-                 output_uncertainty: bool = False, **kw) -> RollingDepthOutput:
+                 output_uncertainty: bool = False, merge: str = "mean", **kw) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:78-176.  `input_video_path` (or the fork's `input_fg_video_path`):
         a video file (decoding needs PyAV, absent from this image), decoded uint8 rgb24 frames
         [N, H, W, 3] (numpy / torch: resized to processing_res and normalised on the device,
         video_io.load_video_frames), or an already-normalised float [N, 3, H, W] tensor in [-1, 1]
         (used as is: processing_res and restore_res do not apply to it).  `refine_stride` (the build's own,
-        1 … refine_snippet_len) and `output_uncertainty`: see forward().  restore_res resizes
-        depth_uncertainty as it resizes depth_pred."""
+        1 … refine_snippet_len), `output_uncertainty` and `merge` ("mean" | "median"): see forward().
+        restore_res resizes depth_uncertainty as it resizes depth_pred."""
         check_refine_stride(refine_stride, refine_snippet_len)
         check_output_uncertainty(output_uncertainty)
+        check_merge(merge)
         assert processing_res >= 0
         if processing_res > 1024:
             logging.warning(f"Procssing at high-resolution ({processing_res}) may lead to suboptimal accuracy.")
@@ -610,7 +620,8 @@ class RollingDepthPipeline:
         out = self.forward(frames[None] if frames.dim() == 4 else frames, dilations, cap_dilation, snippet_lengths,
                            init_infer_steps, strides, coalign_kwargs, refine_step, refine_snippet_len,
                            refine_start_dilation, generator, verbose, max_vae_bs, unload_snippet,
-                           refine_stride=refine_stride, output_uncertainty=output_uncertainty, **kw)
+                           refine_stride=refine_stride, output_uncertainty=output_uncertainty,
+                           **(dict(merge=merge) if merge != "mean" else {}), **kw)
         if restore_res:  # rollingdepth_pipeline.py:155-173 (torchvision resize, antialias=True), on the device
             for name in ("input_rgb", "depth_pred") + (("depth_uncertainty",) if output_uncertainty else ()):
                 t = getattr(out, name)
@@ -624,7 +635,7 @@ class RollingDepthPipeline:
 
     def _forward_sharded(self, input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs, refine_step,
                          refine_snippet_len, refine_start_dilation, init_noise, record, generator=None, strides=1,
-                         refine_stride: int = 1, output_uncertainty: bool = False):
+                         refine_stride: int = 1, output_uncertainty: bool = False, merge: str = "mean"):
         """forward() over W ranks (shard.sharded_forward), outputs assembled on every rank.  Dilations
         arrive already capped and strides validated (forward's checks ran); the snippets are all-gathered
         at full resolution only here, to honour the snippet_ls contract (bench.py keeps them distributed)."""
@@ -638,7 +649,7 @@ class RollingDepthPipeline:
                              gather=True, record=record, generator=generator,
                              init_infer_steps=list(init_infer_steps),
                              strides=list(strides) if isinstance(strides, (list, tuple)) else strides,
-                             refine_stride=refine_stride, output_uncertainty=output_uncertainty)
+                             refine_stride=refine_stride, output_uncertainty=output_uncertainty, merge=merge)
         snips = gather_rows_by_dilation([r.to(self.dtype) for r in so.snippet_rows], so.snippet_counts, world,
                                         self._group)
         H, W = so.depth_pred_full.shape[-2:]
@@ -658,7 +669,7 @@ class RollingDepthPipeline:
                 refine_start_dilation: int, generator: Union[torch.Generator, None], verbose: bool,
                 max_vae_bs: int, unload_snippet: bool, init_noise: Optional[torch.Tensor] = None,
                 record: Optional[dict] = None, refine_stride: int = 1,
-                output_uncertainty: bool = False) -> RollingDepthOutput:
+                output_uncertainty: bool = False, merge: str = "mean") -> RollingDepthOutput:
         """rollingdepth_pipeline.py:193-353.  `refine_stride` (the build's own, 1 … refine_snippet_len):
         each refine step starts its snippets that many positions apart inside every residue class mod the
         step's dilation (refine_snippet_indice), so a frame passes the UNet about refine_snippet_len /
@@ -666,9 +677,16 @@ class RollingDepthPipeline:
         `output_uncertainty` (the build's own): also return RollingDepthOutput.depth_uncertainty, the
         per-pixel spread of the co-aligned snippets around depth_coaligned (one fused merge kernel in place
         of the merge; every other output is bitwise unchanged).  With refine_step > 0 it still describes
-        the co-aligned stage."""
+        the co-aligned stage.
+        `merge` (the build's own, "mean" | "median"; anything else is a ValueError): how the co-aligned snippet
+        predictions that cover a pixel are combined.  "mean" is the reference's merge.  "median" takes their
+        per-pixel median (the mean of the two middle ones for an even count), which one badly aligned snippet
+        cannot move; depth_coaligned is then the renormalised median map, the refine stage starts from it, and
+        depth_uncertainty is the predictions' median absolute deviation around it — the raw MAD, no 1.4826
+        factor — scaled like the standard deviation.  snippet_ls is untouched."""
         refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
         check_output_uncertainty(output_uncertainty)
+        check_merge(merge)
         # ----------------- checks (rollingdepth_pipeline.py:214-252)
         assert 1 in dilations, "dilations should include 1"
         assert len(snippet_lengths) == len(set(snippet_lengths)), f"Repeated values found in {snippet_lengths = }"
@@ -720,7 +738,7 @@ class RollingDepthPipeline:
             if dist.get_world_size(self._group) > 1:
                 return self._forward_sharded(input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs,
                                              refine_step, refine_snippet_len, refine_start_dilation, init_noise,
-                                             record, generator, strides, refine_stride, output_uncertainty)
+                                             record, generator, strides, refine_stride, output_uncertainty, merge)
         # ----------------- encode (H2D boundary :263)
         frames = input_frames[0].to(self.device)
         # input_rgb = frames / 2 + 0.5 in f16 as the reference computes it on the host (x/2 is exact,
@@ -745,7 +763,7 @@ class RollingDepthPipeline:
         merged, scales, trans, hist, *spread = aligner.run(
             [s.view(s.shape[0], s.shape[1], 1, H, W) for s in snippets], dilations,
             strides=strides if strided else None, sequence_length=N if strided else None, merged_f32=self.merge_f32,
-            uncertainty=output_uncertainty)
+            uncertainty=output_uncertainty, **(dict(merge=merge) if merge != "mean" else {}))
         d = merged.float().contiguous()
         mm = K.minmax(d)
         K.renormalize_(d, mm)

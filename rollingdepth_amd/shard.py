@@ -270,8 +270,114 @@ def merge_exchange_plan(counts: Sequence[int], strides: Sequence[int], w: Sequen
     return ranges[rank], send, recv
 
 
+class TermsPlan:
+    """terms_exchange_plan's result: ranges (this rank's frame ranges [lo, hi)), row_counts (its local term
+    count per frame of those ranges, in frame order), row_off (their exclusive running sum, one entry more),
+    send / recv (rows to / from each rank), frame_off / row_idx (per frame of this rank's chunk the rows of the
+    received buffer that hold its terms, source ranks in order; frame_off has one entry more), max_count (the
+    largest cover count of a frame of the chunk)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def terms_exchange_plan(counts: Sequence[int], strides: Sequence[int], w: Sequence[int], N: int, world: int,
+                        rank: int, start_steps: Optional[Sequence[int]] = None) -> TermsPlan:
+    """The all-to-all of the windowed median merge, from the plan alone (no communication).  A median is not a
+    sum, so the ranks exchange the terms themselves: a rank holds, for every frame of its frame ranges
+    (merge_exchange_plan's), one row per (dilation, slot) of its own snippets that covers the frame, frames in
+    order and a frame's rows in the merge's (d ascending, j descending) order.  The rows inside rank q's frame
+    chunk are contiguous and go to q; the owner of a frame finds its terms in the received buffer (source ranks
+    back to back) at row_idx[frame_off[i] : frame_off[i + 1]].  start_steps: as frame_ranges."""
+    from .aligner import snippet_count, snippet_start
+
+    nd = len(counts)
+    ss = [int(s) for s in start_steps] if start_steps is not None else [1] * nd
+    if len(ss) != nd:
+        raise ValueError(f"start steps {ss} need one entry per dilation ({nd})")
+    for d in range(nd):
+        if snippet_count(N, w[d], strides[d], ss[d]) != counts[d]:
+            raise ValueError(f"dilation {d}: {counts[d]} snippets, but start step {ss[d]} over {N} frames (length "
+                             f"{w[d]}, frame stride {strides[d]}) gives {snippet_count(N, w[d], strides[d], ss[d])}")
+    at = [{snippet_start(k, N, w[d], strides[d], ss[d]): k for k in range(counts[d])} for d in range(nd)]
+    chunks = chunk_bounds(N, world)
+    ranges, local = [], []  # per rank: its frame ranges, and frame → its local term count
+    for r in range(world):
+        sub = rank_subsets(counts, world, r)
+        own = [set(x) for x in sub]
+        rg = frame_ranges(sub, strides, w, start_steps, N)
+        ranges.append(rg)
+        local.append({f: sum(1 for d in range(nd) for j in range(w[d]) if at[d].get(f - j * strides[d]) in own[d])
+                      for a, b in rg for f in range(a, b)})
+    mine = [f for a, b in ranges[rank] for f in range(a, b)]
+    row_counts = [local[rank][f] for f in mine]
+    row_off = [0]
+    for c in row_counts:
+        row_off.append(row_off[-1] + c)
+    send = [sum(local[rank][f] for f0, m in _cut(ranges[rank], *chunks[q]) for f in range(f0, f0 + m))
+            for q in range(world)]
+    f0, f1 = chunks[rank]
+    recv, where, o = [], {f: [] for f in range(f0, f1)}, 0
+    for s in range(world):
+        got = 0
+        for a, m in _cut(ranges[s], f0, f1):
+            for f in range(a, a + m):
+                where[f].extend(range(o + got, o + got + local[s][f]))
+                got += local[s][f]
+        recv.append(got)
+        o += got
+    frame_off, row_idx = [0], []
+    for f in range(f0, f1):
+        row_idx.extend(where[f])
+        frame_off.append(len(row_idx))
+    max_count = max([b - a for a, b in zip(frame_off, frame_off[1:])], default=0)
+    return TermsPlan(ranges=ranges[rank], row_counts=row_counts, row_off=row_off, send=send, recv=recv,
+                     frame_off=frame_off, row_idx=row_idx, max_count=max_count)
+
+
+def _pinned_index(values, device) -> torch.Tensor:
+    """int32 index list → device tensor through pinned memory, without a host sync (as
+    RollingDepthPipeline._device_index)."""
+    t = torch.tensor(values, dtype=torch.int32).pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+def _merge_windowed_median(rows, k0, counts, scales, trans, strides, slens, N: int, HW: int, shift, x_f32, group,
+                           start_steps, mad: bool):
+    """_merge_windowed(median=True): this rank's terms [rows, HW] f32 over its frame ranges, the all-to-all of
+    terms_exchange_plan, and the per-pixel selection over each frame's received rows."""
+    from . import kernels as K
+
+    world, rank = _world(group), _rank(group)
+    plan = terms_exchange_plan(counts, strides, slens, N, world, rank, start_steps)
+    f0, f1 = chunk_bounds(N, world)[rank]
+    steps = list(start_steps) if start_steps is not None else None
+    dev = shift.device
+    # every call's own offsets (they start at 0 in each frame range), one upload
+    offs, o = [], 0
+    for a, b in plan.ranges:
+        base = plan.row_off[o]
+        offs.append([v - base for v in plan.row_off[o:o + b - a + 1]])
+        o += b - a
+    tables = _pinned_index([v for t in offs for v in t] + plan.frame_off + plan.row_idx, dev)
+    terms = torch.empty((plan.row_off[-1], HW), dtype=F32, device=dev)
+    o = t0 = 0
+    for (a, b), off in zip(plan.ranges, offs):
+        base = plan.row_off[o]
+        K.aligner_merge_partial_window_terms([r if r.shape[0] else None for r in rows], k0, counts, scales, trans,
+                                             strides, slens, a, b - a, HW, shift, x_f32, N,
+                                             tables[t0:t0 + len(off)], terms[base:base + off[-1]], start_steps=steps)
+        o += b - a
+        t0 += len(off)
+    rbuf = exchange_window_rows(terms, plan.send, plan.recv, group)
+    frame_off = tables[t0:t0 + len(plan.frame_off)]
+    row_idx = tables[t0 + len(plan.frame_off):]
+    return K.aligner_median_rows(rbuf, frame_off, row_idx, f1 - f0, max(plan.max_count, 1), mad=mad)
+
+
 def _merge_windowed(rows, k0, counts, scales, trans, strides, slens, N: int, HW: int, shift, x_f32, group,
-                    start_steps: Optional[Sequence[int]] = None, moments: bool = False):
+                    start_steps: Optional[Sequence[int]] = None, moments: bool = False, median: bool = False,
+                    mad: bool = False):
     """merge_scaled_triplets over W ranks: per-rank f64 sums of only the frames its snippets cover, an
     all-to-all of the rows each rank's frame chunk needs (uneven row counts; RCCL over xGMI), then
     the received pieces added per frame in source-rank order and ÷ the cover count (f64 sums: the
@@ -280,9 +386,16 @@ def _merge_windowed(rows, k0, counts, scales, trans, strides, slens, N: int, HW:
     start_steps (None or all ones: the start-step-1 calls): frames between snippet starts per dilation.
     moments=True: the same plan over f64 rows [2, HW] per frame (Σ then Σ of squares of the terms: twice
     the bytes, a frame still one row of the all-to-all) through the _moments calls → (mean chunk, std
-    chunk), both [f1 − f0, HW] f32; the mean as above, the std the spread of the frame's covering terms."""
+    chunk), both [f1 − f0, HW] f32; the mean as above, the std the spread of the frame's covering terms.
+    median=True: the per-pixel median in place of the mean.  A median is not a sum, so the f64-sum all-to-all
+    cannot carry it: the ranks exchange the terms themselves, [rows, HW] f32 with one row per covering
+    (dilation, slot) (terms_exchange_plan), and the owner selects per pixel over a frame's received rows →
+    the median chunk, or with mad=True (median chunk, MAD chunk); bitwise the single-GPU median merge."""
     from . import kernels as K
 
+    if median:
+        return _merge_windowed_median(rows, k0, counts, scales, trans, strides, slens, N, HW, shift, x_f32, group,
+                                      start_steps, mad)
     world, rank = _world(group), _rank(group)
     ss = dict(start_steps=list(start_steps), seq_len=N) if _strided(start_steps) else {}
     ranges, send, recv = merge_exchange_plan(counts, strides, slens, N, world, rank, start_steps)
@@ -365,7 +478,7 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
                     generator: Optional[torch.Generator] = None,
                     init_infer_steps: Union[int, Sequence[int]] = 1, timing: Optional[list] = None,
                     strides: Union[int, Sequence[int]] = 1, refine_stride: int = 1,
-                    output_uncertainty: bool = False) -> ShardedOutput:
+                    output_uncertainty: bool = False, merge: str = "mean") -> ShardedOutput:
     """Multi-GPU RollingDepthPipeline.forward (every preset: refine_step > 0 included).
 
     `input_frames` is either the whole video [1,N,3,H,W] / [N,3,H,W], or — with `num_frames=N` —
@@ -387,13 +500,17 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     `output_uncertainty`: forward()'s — the windowed merge carries both moments and the output gains
     depth_uncertainty, this rank's chunk [f1 − f0, 1, H, W] f32 of the co-aligned snippets' per-pixel spread
     in depth_coaligned's units (scaled with the all-reduced min / max), and depth_uncertainty_full under
-    `gather`; to_host copies it as the other maps."""
+    `gather`; to_host copies it as the other maps.
+    `merge`: forward()'s ("mean" | "median").  Under "median" the windowed merge exchanges the covering terms
+    themselves (terms_exchange_plan) and each owner takes the per-pixel median of its frames' terms, bitwise
+    the single-GPU median merge; depth_uncertainty is then their raw MAD (no 1.4826 factor)."""
     from . import kernels as K
     from .aligner import DepthAligner, check_row_layout, snippet_count, snippet_last, snippet_start
-    from .pipeline import check_output_uncertainty, check_refine_stride
+    from .pipeline import check_merge, check_output_uncertainty, check_refine_stride
 
     refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
     check_output_uncertainty(output_uncertainty)
+    check_merge(merge)
 
     if group is None:
         group = dist.group.WORLD
@@ -487,7 +604,9 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     _mark(timing, "aligner")
     merged = _merge_windowed(rows, k0, counts, scales, trans, frame_steps, slens, N, H * W, shift,
                              1 if rows_f32 else (2 if pipe.merge_f32 else 0), group,
-                             start_steps if strided else None, moments=output_uncertainty)
+                             start_steps if strided else None,
+                             **(dict(median=True, mad=output_uncertainty) if merge == "median"
+                                else dict(moments=output_uncertainty)))
     spread = None
     if output_uncertainty:
         merged, spread = merged
