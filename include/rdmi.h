@@ -550,6 +550,61 @@ int rdmi_depth_errors(const void* pred, int pred_dtype, const void* target, int 
                       const unsigned char* mask, int N, long P, float lo, float hi, const double* st, float clip_lo,
                       float clip_hi, double* workspace, double* sums, void* stream);
 
+/* Alignment space (since rdmi_version 8): the fit taken against φ(target) and the aligned value brought back to
+ * depth through φ⁻¹ — the protocol for ground truth stored as disparity and for predictors that are affine in
+ * disparity or in log-depth.  φ(g) = g, 1 / g, ln g and φ⁻¹(d) = d, 1 / d, exp d, all in f64 (1 / x the IEEE
+ * division).  An unknown space → RDMI_E_ARG before any launch; RDMI_SPACE_DEPTH launches exactly what the calls
+ * above launch. */
+#define RDMI_SPACE_DEPTH 0
+#define RDMI_SPACE_DISPARITY 1
+#define RDMI_SPACE_LOG 2
+/* rdmi_depth_moments with the six moments taken of (p, φ(g)): n, Σp, Σφ, Σp², Σpφ, Σφ².  Outside RDMI_SPACE_DEPTH a
+ * valid pixel also needs g > 0 (it matters when lo < 0), and p·φ and φ² are rounded products.  rdmi_depth_fit reads
+ * the workspace as it is; its (s, t) then live in the fit space. */
+int rdmi_depth_moments_space(const void* pred, int pred_dtype, const void* target, int target_dtype,
+                             const unsigned char* mask, int N, long P, float lo, float hi, int space,
+                             double* workspace, void* stream);
+/* rdmi_depth_errors with a = φ⁻¹(d), d = fma(s, p, t) (one rounding, as above), then clamped to [clip_lo, clip_hi];
+ * the same eight sums against g, in depth; validity as in rdmi_depth_moments_space.  RDMI_SPACE_DISPARITY: d ≤ 0 has
+ * no finite depth and gives a = +inf, which the clamp brings to clip_hi.  With clip_hi = +inf such a pixel stays
+ * in n, counts as above every δ threshold, and the four error sums become inf: name a depth cap. */
+int rdmi_depth_errors_space(const void* pred, int pred_dtype, const void* target, int target_dtype,
+                            const unsigned char* mask, int N, long P, float lo, float hi, const double* st, int space,
+                            float clip_lo, float clip_hi, double* workspace, double* sums, void* stream);
+
+/* Temporal consistency (since rdmi_version 8): pair i = 0 … N − k − 1 compares frame f = i with frame f' = i + k
+ * (k = frame_step ≥ 1) of pred / target [N][H][W]; target may be NULL (target_dtype is then ignored).
+ *
+ * a(frame, pixel) = φ⁻¹(fma(s, p, t)) clamped to [clip_lo, clip_hi], with that frame's own row of st [N][2]
+ * (rdmi_depth_fit's output for the fit of `space`).  A pixel of a frame is valid by the rule of
+ * rdmi_depth_errors_space; without a target only the mask and the finiteness of pred count, and lo / hi are
+ * ignored.  A pixel of frame f enters pair i when it is valid, pair_mask [N − k][H·W] (u8 or NULL) is ≠ 0 there,
+ * and its sample in f' exists:
+ *   flow == NULL: the same pixel of f', which must be valid in f';
+ *   flow [N − k][H][W][2] = (dx, dy) in pixels, f32: X = x + (double)dx, Y = y + (double)dy, x0 = floor(X),
+ *     y0 = floor(Y), wx = X − x0, wy = Y − y0; the taps (y0 + i, x0 + j) carry the weights
+ *     (1 − wy | wy)·(1 − wx | wx).  A tap of weight exactly 0 is neither read nor required; every other tap must lie
+ *     inside the frame and be valid in f', else the pixel is left out, as it is for a non-finite dx or dy.  No
+ *     address is formed from a tap outside the frame.  a' = (1 − wy)·((1 − wx)·a₀₀ + wx·a₀₁) + wy·((1 − wx)·a₁₀ +
+ *     wx·a₁₁) of the taps' aligned, clamped values, each operation rounded once, terms of weight 0 left out: a
+ *     single tap of weight 1 gives a' = a_tap exactly.  g' is the same formula on the taps' targets.
+ * With Δa = a' − a and Δg = g' − g, sums [N − k][8] (out) = n, Σ|Δa|, ΣΔa², Σ|Δa − Δg|, Σ(Δa − Δg)², Σ|Δg|, ΣΔg²,
+ * ΣΔa·Δg per pair (the last five 0 without a target).  A pair one of whose two st rows holds a NaN contributes
+ * nothing: its row is zero, n included.
+ *
+ * workspace ≥ rdmi_depth_metrics_workspace(N − k, H·W) doubles.  The tiling, the lane assignment over frame f and
+ * the two-stage reduction are those of the passes above (grid (blocks per frame, N − k), no atomics), so the same
+ * inputs give the same bits on every call, for a pair evaluated alone or inside a longer video, and for
+ * 16-byte-aligned or unaligned bases.  Frame f is read with 16-byte loads, the taps of f' with scalar loads.
+ *
+ * RDMI_E_ARG before any launch: a null pred / st / workspace / sums, N < 2, H or W < 1, frame_step < 1 or ≥ N, a
+ * dtype other than RDMI_F16 / RDMI_F32, an unknown space, lo ≥ hi with a target, clip_lo > clip_hi (a NaN bound
+ * fails both tests).  N − frame_step ≤ 65535 (RDMI_E_UNSUPPORTED beyond). */
+int rdmi_depth_temporal(const void* pred, int pred_dtype, const void* target, int target_dtype,
+                        const unsigned char* mask, const float* flow, const unsigned char* pair_mask, int N, int H,
+                        int W, int frame_step, float lo, float hi, const double* st, int space, float clip_lo,
+                        float clip_hi, double* workspace, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 Public surface mirrors the reference: RollingDepthPipeline / RollingDepthOutput
 (rollingdepth/rollingdepth_pipeline.py), DepthAligner (rollingdepth/depth_aligner.py) and the
 modified diffusers attention processor (CrossFrameAttnProcessor); depth_metrics / align_scale_shift
-(metrics.py) score a depth video after a least-squares scale and shift.  All arithmetic runs in
+(metrics.py) score a depth video after a least-squares scale and shift, temporal_metrics its change
+from frame to frame.  All arithmetic runs in
 librdmi.so (HIP); importing the compute modules without the built library raises.
 """
 __version__ = "0.1.0"
@@ -19,7 +20,7 @@ def __getattr__(name):
     if name == "CrossFrameAttnProcessor":
         from .attention_processor import CrossFrameAttnProcessor
         return CrossFrameAttnProcessor
-    if name in ("depth_metrics", "align_scale_shift", "DepthMetrics"):
+    if name in ("depth_metrics", "align_scale_shift", "DepthMetrics", "temporal_metrics", "TemporalMetrics"):
         from . import metrics
         return getattr(metrics, name)
     raise AttributeError(name)

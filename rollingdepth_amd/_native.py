@@ -142,10 +142,15 @@ _SIGS = {
     "rdmi_depth_moments": (i32, [vp, i32, vp, i32, vp, i32, i64, f32, f32, vp, vp]),
     "rdmi_depth_fit": (i32, [vp, i32, i64, i32, vp, vp, vp]),
     "rdmi_depth_errors": (i32, [vp, i32, vp, i32, vp, i32, i64, f32, f32, vp, f32, f32, vp, vp, vp]),
+    "rdmi_depth_moments_space": (i32, [vp, i32, vp, i32, vp, i32, i64, f32, f32, i32, vp, vp]),
+    "rdmi_depth_errors_space": (i32, [vp, i32, vp, i32, vp, i32, i64, f32, f32, vp, i32, f32, f32, vp, vp, vp]),
+    "rdmi_depth_temporal": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, f32, f32, vp,
+                                  vp, vp]),
 }
 
 RDMI_F16, RDMI_F32, RDMI_U8, RDMI_F32_X3, RDMI_F32_X6 = 0, 1, 2, 3, 4
 RDMI_FIT_NONE, RDMI_FIT_FRAME, RDMI_FIT_VIDEO = 0, 1, 2
+RDMI_SPACE_DEPTH, RDMI_SPACE_DISPARITY, RDMI_SPACE_LOG = 0, 1, 2
 RDMI_RESIZE_NEAREST, RDMI_RESIZE_BILINEAR, RDMI_RESIZE_BICUBIC = 0, 1, 2
 
 EXPORTED = tuple(_SIGS)

@@ -1383,6 +1383,7 @@ def resize(x: torch.Tensor, size, mode: str = "BILINEAR", normalize: bool = Fals
 
 # ----------------------------------------------------------------------------- depth metrics
 DEPTH_FIT_MODES = {"none": _N.RDMI_FIT_NONE, "frame": _N.RDMI_FIT_FRAME, "video": _N.RDMI_FIT_VIDEO}
+DEPTH_SPACES = {"depth": _N.RDMI_SPACE_DEPTH, "disparity": _N.RDMI_SPACE_DISPARITY, "log": _N.RDMI_SPACE_LOG}
 
 
 def _depth_inputs(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], what: str):
@@ -1417,11 +1418,16 @@ def _depth_ws(ws: Optional[torch.Tensor], N: int, P: int, device) -> torch.Tenso
 
 
 def depth_moments(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], lo: float, hi: float,
-                  ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Per-workgroup moment sums of pred / target [N, P] (f16 or f32 each; mask u8 [N, P] or None) over the
-    valid pixels → the workspace depth_fit reads."""
+                  ws: Optional[torch.Tensor] = None, space: int = 0) -> torch.Tensor:
+    """Per-workgroup moment sums of pred / φ(target) [N, P] (f16 or f32 each; mask u8 [N, P] or None) over the
+    valid pixels → the workspace depth_fit reads.  space: a DEPTH_SPACES value; 0 is the call of old."""
     N, P = _depth_inputs(pred, target, mask, "depth_moments")
     ws = _depth_ws(ws, N, P, pred.device)
+    if space:
+        check(lib.rdmi_depth_moments_space(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target),
+                                           _p(mask), N, P, lo, hi, space, ws.data_ptr(), _stream()),
+              "rdmi_depth_moments_space")
+        return ws
     check(lib.rdmi_depth_moments(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target), _p(mask),
                                  N, P, lo, hi, ws.data_ptr(), _stream()), "rdmi_depth_moments")
     return ws
@@ -1440,15 +1446,54 @@ def depth_fit(ws: Optional[torch.Tensor], N: int, P: int, mode: int, device=None
 
 def depth_errors(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], st: torch.Tensor,
                  lo: float, hi: float, clip_lo: float = -math.inf, clip_hi: float = math.inf,
-                 ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Error sums of fma(s, pred, t) against target → f64 [N, 8] (rdmi.h rdmi_depth_errors); st f64 [N, 2]."""
+                 ws: Optional[torch.Tensor] = None, space: int = 0) -> torch.Tensor:
+    """Error sums of φ⁻¹(fma(s, pred, t)) against target → f64 [N, 8] (rdmi.h rdmi_depth_errors, _space); st f64
+    [N, 2].  space: a DEPTH_SPACES value; 0 is the call of old."""
     N, P = _depth_inputs(pred, target, mask, "depth_errors")
     _need(st, torch.float64, "depth_errors.st")
     if st.shape != (N, 2) or not st.is_contiguous():
         raise ValueError(f"depth_errors.st: contiguous [N, 2] expected, got {tuple(st.shape)}")
     ws = _depth_ws(ws, N, P, pred.device)
     sums = torch.empty((N, 8), dtype=torch.float64, device=pred.device)
+    if space:
+        check(lib.rdmi_depth_errors_space(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target),
+                                          _p(mask), N, P, lo, hi, st.data_ptr(), space, clip_lo, clip_hi,
+                                          ws.data_ptr(), sums.data_ptr(), _stream()), "rdmi_depth_errors_space")
+        return sums
     check(lib.rdmi_depth_errors(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target), _p(mask),
                                 N, P, lo, hi, st.data_ptr(), clip_lo, clip_hi, ws.data_ptr(), sums.data_ptr(),
                                 _stream()), "rdmi_depth_errors")
+    return sums
+
+
+def depth_temporal(pred: torch.Tensor, target: Optional[torch.Tensor], mask: Optional[torch.Tensor],
+                   flow: Optional[torch.Tensor], pair_mask: Optional[torch.Tensor], st: torch.Tensor, H: int, W: int,
+                   frame_step: int = 1, lo: float = 1e-3, hi: float = math.inf, space: int = 0,
+                   clip_lo: float = -math.inf, clip_hi: float = math.inf, ws: Optional[torch.Tensor] = None
+                   ) -> torch.Tensor:
+    """Sums of the change between frame i and frame i + frame_step → f64 [N − frame_step, 8] (rdmi.h
+    rdmi_depth_temporal).  pred, target (or None), mask (u8 or None) [N, H·W]; flow f32 [N − k, H, W, 2] or None;
+    pair_mask u8 [N − k, H·W] or None; st f64 [N, 2]."""
+    N, P = _depth_inputs(pred, pred if target is None else target, mask, "depth_temporal")
+    if P != H * W:
+        raise ValueError(f"depth_temporal: H·W = {H}·{W} does not match pred's {P} pixels per frame")
+    pairs = max(N - frame_step, 0)
+    _need(st, torch.float64, "depth_temporal.st")
+    if st.shape != (N, 2) or not st.is_contiguous():
+        raise ValueError(f"depth_temporal.st: contiguous [N, 2] expected, got {tuple(st.shape)}")
+    if flow is not None:
+        _need(flow, torch.float32, "depth_temporal.flow")
+        if flow.shape != (pairs, H, W, 2) or not flow.is_contiguous():
+            raise ValueError(f"depth_temporal.flow: contiguous [N - k, H, W, 2] expected, got {tuple(flow.shape)}")
+    if pair_mask is not None:
+        _need(pair_mask, torch.uint8, "depth_temporal.pair_mask")
+        if pair_mask.shape != (pairs, P) or not pair_mask.is_contiguous():
+            raise ValueError(f"depth_temporal.pair_mask: contiguous [N - k, P] expected, got "
+                             f"{tuple(pair_mask.shape)}")
+    ws = _depth_ws(ws, pairs, P, pred.device)
+    sums = torch.empty((pairs, 8), dtype=torch.float64, device=pred.device)
+    check(lib.rdmi_depth_temporal(pred.data_ptr(), _dtype_code(pred), _p(target),
+                                  _dtype_code(pred if target is None else target), _p(mask), _p(flow), _p(pair_mask),
+                                  N, H, W, frame_step, lo, hi, st.data_ptr(), space, clip_lo, clip_hi, ws.data_ptr(),
+                                  sums.data_ptr(), _stream()), "rdmi_depth_temporal")
     return sums

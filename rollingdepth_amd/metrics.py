@@ -9,8 +9,16 @@ frame, and reports AbsRel and δ < 1.25ᵏ on the valid pixels:
     m = depth_metrics(pred, target, mask, align="frame")  # one fit per frame
     m.abs_rel, m.delta1, m.scale, m.shift
 
-All sums run in librdmi (rdmi_depth_moments / _fit / _errors, f64, fixed summation order: the same inputs
-give the same bits on every call); this module only validates, reshapes and does the last few host
+The fit can also be taken in disparity or log-depth (space="disparity" | "log": against 1 / target or
+ln target, the aligned value brought back to depth before the errors), and temporal_metrics scores the change
+from frame to frame — flicker, and the temporal-gradient error against the target's own change — optionally
+along an optical flow the caller supplies:
+
+    t = temporal_metrics(pred, target, mask, flow=flow)   # flow [N − 1, H, W, 2], (dx, dy) in pixels
+    t.flicker, t.tge, t.change_corr
+
+All sums run in librdmi (rdmi_depth_moments / _fit / _errors / _temporal, f64, fixed summation order: the same
+inputs give the same bits on every call); this module only validates, reshapes and does the last few host
 divisions.
 """
 from __future__ import annotations
@@ -22,6 +30,7 @@ from typing import List, Optional, Tuple
 import torch
 
 ALIGN_MODES = ("video", "frame", "none")
+SPACES = ("depth", "disparity", "log")
 
 
 @dataclass
@@ -42,10 +51,15 @@ class DepthMetrics:
     frames_skipped: List[int]  # frames without a fit (NaN scale / shift): they contribute nothing
 
 
-def _prepare(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], valid_range
-             ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], float, float]:
-    """Validate (before any device work) and bring the operands to contiguous [N, P] tensors on the device."""
+def _prepare(pred: torch.Tensor, target: Optional[torch.Tensor], mask: Optional[torch.Tensor], valid_range,
+             more_checks=None
+             ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor], float, float]:
+    """Validate (before any device work) and bring the operands to contiguous [N, P] tensors on the device.
+    target None is temporal_metrics' call without one; more_checks((N, H, W)) are its further checks, run after
+    these and still before any device work."""
     for t, name in ((pred, "pred"), (target, "target")):
+        if t is None:
+            continue
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name}: a tensor expected, got {type(t).__name__}")
         if t.dtype not in (torch.float16, torch.float32):
@@ -72,8 +86,10 @@ def _prepare(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tens
     lo, hi = (float(v) for v in valid_range)
     if not lo < hi:
         raise ValueError(f"valid_range: lo < hi expected, got ({lo}, {hi})")
+    if more_checks is not None:
+        more_checks(shape)
 
-    dev = pred.device if pred.is_cuda else (target.device if target.is_cuda else torch.device("cuda", 0))
+    dev = _device(pred, target)
 
     def flat(t):
         return t.to(dev).contiguous().view(shape[0], shape[1] * shape[2])
@@ -83,7 +99,26 @@ def _prepare(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tens
         m = flat(mask)
         if m.dtype == torch.bool:
             m = m.view(torch.uint8)
-    return flat(pred), flat(target), m, lo, hi
+    return flat(pred), None if target is None else flat(target), m, lo, hi
+
+
+def _device(pred: torch.Tensor, target: Optional[torch.Tensor]) -> torch.device:
+    if pred.is_cuda:
+        return pred.device
+    return target.device if target is not None and target.is_cuda else torch.device("cuda", 0)
+
+
+def _space_and_clip(space, clip) -> Tuple[float, float]:
+    """The checks depth_metrics and temporal_metrics share → (clip_lo, clip_hi)."""
+    if space not in SPACES:
+        raise ValueError(f"space: one of {SPACES} expected, got {space!r}")
+    clip_lo, clip_hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
+    if not clip_lo <= clip_hi:
+        raise ValueError(f"clip: lo <= hi expected, got ({clip_lo}, {clip_hi})")
+    if space == "disparity" and math.isinf(clip_hi):
+        raise ValueError("clip: space='disparity' needs a finite upper clip (a non-positive aligned disparity has no "
+                         f"finite depth: name the depth cap), got {clip}")
+    return clip_lo, clip_hi
 
 
 def _pool(per_frame: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> DepthMetrics:
@@ -104,7 +139,7 @@ def _pool(per_frame: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> 
 
 
 def align_scale_shift(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                      per_frame: bool = False, valid_range=(1e-3, math.inf)
+                      per_frame: bool = False, valid_range=(1e-3, math.inf), space: str = "depth"
                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Least-squares (scale, shift) of pred onto target over the valid pixels — mask ≠ 0, both finite,
     valid_range[0] < target < valid_range[1] — for the whole video, or per frame.
@@ -112,38 +147,156 @@ def align_scale_shift(pred: torch.Tensor, target: torch.Tensor, mask: Optional[t
     pred, target: [N, H, W] or [N, 1, H, W], f16 or f32, on the host or the device (host tensors are moved to
     cuda:0); mask: bool / uint8 of the same shape.  Returns host tensors (scale f64 [N], shift f64 [N],
     moments f64 [N, 6] = n, Σp, Σg, Σp², Σpg, Σg² per frame); the video fit is repeated in every row.  A frame
-    (video) with fewer than two valid pixels or a constant pred has no fit: NaN."""
+    (video) with fewer than two valid pixels or a constant pred has no fit: NaN.
+
+    space: "depth", "disparity" or "log" — the fit is of pred onto φ(target) = target, 1 / target or ln target
+    (valid pixels then also need target > 0), and scale, shift and the moments (with g = φ(target)) are those of
+    that space."""
+    if space not in SPACES:
+        raise ValueError(f"space: one of {SPACES} expected, got {space!r}")
     p, g, m, lo, hi = _prepare(pred, target, mask, valid_range)
     from . import kernels as K
 
-    ws = K.depth_moments(p, g, m, lo, hi)
+    ws = K.depth_moments(p, g, m, lo, hi, space=K.DEPTH_SPACES[space])
     moments, st = K.depth_fit(ws, p.shape[0], p.shape[1], K.DEPTH_FIT_MODES["frame" if per_frame else "video"])
     st = st.cpu()
     return st[:, 0].contiguous(), st[:, 1].contiguous(), moments.cpu()
 
 
 def depth_metrics(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                  align: str = "video", valid_range=(1e-3, math.inf), clip: Optional[Tuple[float, float]] = None
-                  ) -> DepthMetrics:
+                  align: str = "video", valid_range=(1e-3, math.inf), clip: Optional[Tuple[float, float]] = None,
+                  space: str = "depth") -> DepthMetrics:
     """AbsRel, SqRel, MAE, RMSE and δ < 1.25ᵏ of scale·pred + shift against target on the valid pixels.
 
     align: "video" (one least-squares fit for all frames), "frame" (one per frame) or "none" (pred as it is).
     clip: (lo, hi) clamps the aligned prediction — never the target — before the errors are taken.  Inputs as
     for align_scale_shift.  Frames without a fit are left out and listed in frames_skipped; with no valid
-    pixel at all every metric is NaN."""
+    pixel at all every metric is NaN.
+
+    space: the fit is taken in "depth", "disparity" or "log" space (see align_scale_shift) and the aligned value
+    a = φ⁻¹(scale·pred + shift) — the value itself, its reciprocal or its exponential — is compared with the
+    target in depth; scale and shift stay those of the fit space.  "disparity" needs a clip with a finite upper
+    bound: an aligned disparity ≤ 0 has no finite depth and is taken to the cap."""
     if align not in ALIGN_MODES:
         raise ValueError(f"align: one of {ALIGN_MODES} expected, got {align!r}")
-    clip_lo, clip_hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
-    if not clip_lo <= clip_hi:
-        raise ValueError(f"clip: lo <= hi expected, got ({clip_lo}, {clip_hi})")
+    clip_lo, clip_hi = _space_and_clip(space, clip)
     p, g, m, lo, hi = _prepare(pred, target, mask, valid_range)
     from . import kernels as K
 
     N, P = p.shape
+    sp = K.DEPTH_SPACES[space]
     ws = K.depth_metrics_workspace(N, P, p.device)
     if align != "none":
-        K.depth_moments(p, g, m, lo, hi, ws)
+        K.depth_moments(p, g, m, lo, hi, ws, space=sp)
     _, st = K.depth_fit(ws if align != "none" else None, N, P, K.DEPTH_FIT_MODES[align], device=p.device)
-    sums = K.depth_errors(p, g, m, st, lo, hi, clip_lo, clip_hi, ws)
+    sums = K.depth_errors(p, g, m, st, lo, hi, clip_lo, clip_hi, ws, space=sp)
     st = st.cpu()
     return _pool(sums.cpu(), st[:, 0].contiguous(), st[:, 1].contiguous())
+
+
+@dataclass
+class TemporalMetrics:
+    """Pooled over all valid pixels of all pairs (each pair's sums added in pair order, ÷ n_valid).  Pair i is
+    frame i against frame i + frame_step; Δa and Δg are the changes of the aligned prediction and of the target
+    between the two.  Without a target the four target-based fields are NaN."""
+    flicker: float         # mean |Δa|
+    flicker_rmse: float    # sqrt(mean Δa²)
+    tge: float             # temporal-gradient error: mean |Δa − Δg|
+    tge_rmse: float        # sqrt(mean (Δa − Δg)²)
+    target_change: float   # mean |Δg|
+    change_corr: float     # ΣΔa·Δg / sqrt(ΣΔa² · ΣΔg²); NaN when either factor is 0
+    n_valid: int
+    scale: torch.Tensor      # f64 [N], host
+    shift: torch.Tensor      # f64 [N], host
+    # f64 [N − frame_step, 8], host: n, Σ|Δa|, ΣΔa², Σ|Δa−Δg|, Σ(Δa−Δg)², Σ|Δg|, ΣΔg², ΣΔa·Δg
+    per_pair: torch.Tensor
+    pairs_skipped: List[int]  # pairs with a frame without a fit (NaN scale / shift): they contribute nothing
+
+
+def _pool_temporal(per_pair: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, frame_step: int,
+                   has_target: bool = True) -> TemporalMetrics:
+    """Host tensors (f64 [N − k, 8] pair sums, f64 [N] scale / shift) → TemporalMetrics."""
+    tot = [0.0] * 8
+    for row in per_pair.tolist():  # pair order, f64
+        for k in range(8):
+            tot[k] += row[k]
+    n = tot[0]
+    nofit = [math.isnan(s) or math.isnan(t) for s, t in zip(scale.tolist(), shift.tolist())]
+    skipped = [i for i in range(per_pair.shape[0]) if nofit[i] or nofit[i + frame_step]]
+    nan = math.nan
+    flicker = flicker_rmse = tge = tge_rmse = target_change = change_corr = nan
+    if n > 0:
+        flicker, flicker_rmse = tot[1] / n, math.sqrt(tot[2] / n)
+        if has_target:
+            tge, tge_rmse, target_change = tot[3] / n, math.sqrt(tot[4] / n), tot[5] / n
+            if tot[2] > 0 and tot[6] > 0:
+                change_corr = tot[7] / math.sqrt(tot[2] * tot[6])
+    return TemporalMetrics(flicker=flicker, flicker_rmse=flicker_rmse, tge=tge, tge_rmse=tge_rmse,
+                           target_change=target_change, change_corr=change_corr, n_valid=int(n), scale=scale,
+                           shift=shift, per_pair=per_pair, pairs_skipped=skipped)
+
+
+def temporal_metrics(pred: torch.Tensor, target: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                     *, flow: Optional[torch.Tensor] = None, pair_mask: Optional[torch.Tensor] = None,
+                     frame_step: int = 1, align: str = "video", space: str = "depth",
+                     valid_range=(1e-3, math.inf), clip: Optional[Tuple[float, float]] = None) -> TemporalMetrics:
+    """Temporal consistency of a depth video: the change of the aligned prediction a between frame i and frame
+    i + frame_step (flicker) and its difference from the target's own change (temporal-gradient error).
+
+    pred, target, mask, align, space, valid_range and clip as for depth_metrics: the fit is the one depth_metrics
+    takes and every frame is aligned with its own scale and shift.  Without a target there is nothing to fit:
+    align must be "none", only the mask and the finiteness of pred decide validity, and the target-based fields
+    are NaN.  flow: f32 [N − frame_step, H, W, 2], (dx, dy) in pixels from frame i to frame i + frame_step; the
+    later frame is then sampled bilinearly at (x + dx, y + dy), and a pixel whose taps leave the frame or touch
+    an invalid pixel is left out.  Without a flow the same pixel is compared — right for a static camera, an upper
+    bound on flicker otherwise; no flow estimator is part of this package.  pair_mask: bool / uint8
+    [N − frame_step, H, W], pixels of frame i to use in pair i (an occlusion mask).  With no valid pixel at all
+    every metric is NaN."""
+    if align not in ALIGN_MODES:
+        raise ValueError(f"align: one of {ALIGN_MODES} expected, got {align!r}")
+    if target is None and align != "none":
+        raise ValueError(f"align: without a target only 'none' is possible, got {align!r}")
+    clip_lo, clip_hi = _space_and_clip(space, clip)
+    if isinstance(frame_step, bool) or not isinstance(frame_step, int):
+        raise TypeError(f"frame_step: an int expected, got {type(frame_step).__name__}")
+    for t, name, dtypes, what in ((flow, "flow", (torch.float32,), "float32"),
+                                  (pair_mask, "pair_mask", (torch.bool, torch.uint8), "bool or uint8")):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a tensor expected, got {type(t).__name__}")
+        if t.dtype not in dtypes:
+            raise TypeError(f"{name}: {what} expected, got {t.dtype}")
+
+    def pair_checks(shape):
+        N, H, W = shape
+        if not 1 <= frame_step < N:
+            raise ValueError(f"frame_step: 1 <= frame_step < N = {N} expected, got {frame_step}")
+        pairs = N - frame_step
+        if flow is not None and tuple(flow.shape) != (pairs, H, W, 2):
+            raise ValueError(f"flow: shape {tuple(flow.shape)} does not match [N - frame_step, H, W, 2] = "
+                             f"{(pairs, H, W, 2)}")
+        if pair_mask is not None and tuple(pair_mask.shape) not in ((pairs, H, W), (pairs, 1, H, W)):
+            raise ValueError(f"pair_mask: shape {tuple(pair_mask.shape)} does not match [N - frame_step, H, W] = "
+                             f"{(pairs, H, W)}")
+
+    p, g, m, lo, hi = _prepare(pred, target, mask, valid_range, pair_checks)
+    from . import kernels as K
+
+    N, P = p.shape
+    H, W = pred.shape[-2], pred.shape[-1]
+    pairs, dev = N - frame_step, p.device
+    fl = None if flow is None else flow.to(dev).contiguous()
+    pm = None
+    if pair_mask is not None:
+        pm = pair_mask.to(dev).contiguous().view(pairs, P)
+        if pm.dtype == torch.bool:
+            pm = pm.view(torch.uint8)
+    sp = K.DEPTH_SPACES[space]
+    ws = K.depth_metrics_workspace(N, P, dev)  # the moments' N rows; the temporal pass needs N − frame_step
+    if align != "none":
+        K.depth_moments(p, g, m, lo, hi, ws, space=sp)
+    _, st = K.depth_fit(ws if align != "none" else None, N, P, K.DEPTH_FIT_MODES[align], device=dev)
+    sums = K.depth_temporal(p, g, m, fl, pm, st, H, W, frame_step, lo, hi, sp, clip_lo, clip_hi, ws)
+    st = st.cpu()
+    return _pool_temporal(sums.cpu(), st[:, 0].contiguous(), st[:, 1].contiguous(), frame_step, g is not None)

@@ -1,6 +1,6 @@
 """Time the depth-metric passes against the existing streaming reduction (one GPU).
 
-    python tools/metrics_probe.py [--frames 100] [--res 768] [--reps 10] [--warmup 3]
+    python tools/metrics_probe.py [--frames 100] [--res 768] [--reps 10] [--warmup 3] [--temporal]
 
 f32 pred and target [frames, res, res] with a u8 mask, all on the device.  HIP events, the median of `reps`
 after `warmup` calls, for
@@ -10,7 +10,10 @@ after `warmup` calls, for
     and each of the two streaming passes alone,
   * kernels.minmax over pred, the streaming reduction the project already had.
 Bytes are algorithmic: each metric pass reads pred + target + mask once (9 B per pixel), minmax reads 4 B per
-pixel.  One JSON line at the end.
+pixel.  --temporal adds rdmi_depth_temporal (frame_step 1, the fit above) without a flow and with a smooth
+synthetic one (values on the ¼-pixel grid, |dx|, |dy| ≤ 3): both frames' pred, target and mask per pixel pair
+(18 B), plus 8 B of flow.  rdmi_depth_errors in the same run on the same inputs is its yardstick.  One JSON line
+at the end.
 """
 import argparse
 import json
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--res", type=int, default=768)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--temporal", action="store_true", help="add the rdmi_depth_temporal rows")
     a = ap.parse_args()
 
     from rollingdepth_amd import kernels as K
@@ -73,6 +77,24 @@ def main():
         "rdmi_depth_errors": (lambda: K.depth_errors(p2, g2, m2, st, 1e-3, math.inf, ws=ws), 9 * N * P),
         "minmax (f32 pred)": (lambda: K.minmax(pred), 4 * N * P),
     }
+    if a.temporal:
+        # a smooth flow: a slow wave over the frame, drifting from pair to pair, rounded to quarter pixels
+        y, x = torch.meshgrid(torch.arange(a.res, device=dev) / a.res, torch.arange(a.res, device=dev) / a.res,
+                              indexing="ij")
+        ph = torch.arange(N - 1, device=dev).view(-1, 1, 1) * 0.1
+        dx = 3 * torch.sin(2 * math.pi * y + ph) * torch.cos(2 * math.pi * x)
+        dy = 3 * torch.cos(2 * math.pi * y) * torch.sin(2 * math.pi * x + ph)
+        flow = (torch.stack([dx, dy], -1) * 4).round() / 4
+        assert flow.abs().max() <= 3 and flow.shape == (N - 1, a.res, a.res, 2)
+        flow = flow.float().contiguous()
+
+        def temporal(fl):
+            return K.depth_temporal(p2, g2, m2, fl, None, st, a.res, a.res, 1, 1e-3, math.inf, ws=ws)
+
+        kept = [float(temporal(fl)[:, 0].sum().item()) / ((N - 1) * P) for fl in (None, flow)]
+        print(f"rdmi_depth_temporal keeps {kept[0]:.4f} of the pixel pairs without a flow, {kept[1]:.4f} with it")
+        runs["rdmi_depth_temporal, no flow"] = (lambda: temporal(None), 18 * (N - 1) * P)
+        runs["rdmi_depth_temporal, smooth flow"] = (lambda: temporal(flow), 26 * (N - 1) * P)
     out = depth_metrics(pred, target, mask, align="video")
     print(f"{N} x {a.res}^2 f32 pred / target, u8 mask; n_valid {out.n_valid}, scale {out.scale[0].item():.6f}, "
           f"shift {out.shift[0].item():.6f}, abs_rel {out.abs_rel:.6f}, delta1 {out.delta1:.6f}")
