@@ -605,6 +605,50 @@ int rdmi_depth_temporal(const void* pred, int pred_dtype, const void* target, in
                         int W, int frame_step, float lo, float hi, const double* st, int space, float clip_lo,
                         float clip_hi, double* workspace, double* sums, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Exact order statistics (since rdmi_version 9): the value of a given rank among the elements of an f16 / f32
+ * buffer, by a most-significant-digit radix select that reads the data rdmi_select_passes() times, sorts nothing
+ * and never waits on the host.  The robust range of the depth pipeline's renormalisation (percentiles in place of
+ * min / max; the reference has only the latter, rollingdepth_pipeline.py:316-318) and of the colouriser.
+ *
+ * x [n] f32 (x_f32 = 1) or f16 (0, widened exactly), any element-aligned pointer: elements before the first
+ * 16-byte boundary and after the last whole vector are read singly, the rest with 16-byte loads.  mask [n] u8 or
+ * NULL, one byte per element, ≠ 0 = keep.  NaNs are skipped like masked-out elements; −0 counts as +0; ±inf are
+ * ordered like any value.  For a fraction q in [0, 1] and cnt counted values the result is the data value of
+ * 0-based rank floor(q · (double)(cnt − 1)) — no interpolation; numpy's method="lower" whenever both rank formulas
+ * are exact — and NaN when cnt = 0.  Up to RDMI_SELECT_MAX quantiles are found together, so each pass reads the data
+ * once for all of them.  Key, digits, rank rule and the histogram walk: csrc/select_key.h.  All counts are
+ * integers (LDS atomics per wave, one 64-bit global atomic add per workgroup and non-empty bin), so the results
+ * are bitwise reproducible, on one device or summed over many.
+ *
+ * rdmi_select_hist: pass `pass` (0 … rdmi_select_passes() − 1) of the counting.  For quantile j < k it ADDS to
+ *   hist[j][rdmi_select_bins()] (64-bit, zeroed by the caller) the counts, per value of the pass's key digit, of
+ *   the kept elements whose higher digits equal quantile j's prefix in `state`; pass 0 counts every kept element
+ *   and does not read `state`.  Histograms of several buffers (ranks, chunks) may be added before the pick.
+ * rdmi_select_pick: one small launch.  Pass 0 takes cnt = Σ hist[0] and turns each q[j] (f64, device memory)
+ *   into a rank; every pass finds the bin holding quantile j's remaining rank, extends its prefix in `state` and
+ *   keeps the rank inside the bin; the last pass writes the values to out[k] (f32).  `state`: rdmi_select_state_bytes()
+ *   bytes of device memory, 8-byte aligned, written by pass 0 (no initialisation needed).
+ * rdmi_quantiles: the single-device chain zero, hist, pick, hist, pick … on one stream; workspace ≥
+ *   rdmi_quantiles_workspace() bytes, 8-byte aligned (RDMI_E_ALIGN otherwise), no initialisation needed.
+ * RDMI_E_ARG before any launch: a null x / state / hist / q / out / workspace, n ≤ 0, k outside
+ * 1 … RDMI_SELECT_MAX, pass outside its range.  n ≥ 2^42 → RDMI_E_UNSUPPORTED. */
+#define RDMI_SELECT_MAX 4
+int rdmi_select_bins(void);
+int rdmi_select_passes(void);
+long rdmi_select_state_bytes(void);
+long rdmi_quantiles_workspace(void);
+int rdmi_select_hist(const void* x, int x_f32, const unsigned char* mask, long n, const void* state, int pass, int k,
+                     long long* hist, void* stream);
+int rdmi_select_pick(const long long* hist, const double* q, int pass, int k, void* state, float* out, void* stream);
+int rdmi_quantiles(const void* x, int x_f32, const unsigned char* mask, long n, const double* q, int k, float* out,
+                   void* workspace, void* stream);
+/* In place: rdmi_renormalize_f32's arithmetic in its order (v = x − lo; v = v / (hi − lo); v·2 − 1) with
+ * lohi = {lo, hi} read from the device, then clamped to [−1, 1] (a NaN stays NaN).  With lohi = the buffer's
+ * {min, max} the clamp never fires and the result is rdmi_renormalize_f32's, bitwise.  hi = lo divides by zero:
+ * elements equal to lo become NaN, the others ±1. */
+int rdmi_renormalize_clip_f32(float* x, long n, const float* lohi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

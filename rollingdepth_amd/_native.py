@@ -146,6 +146,14 @@ _SIGS = {
     "rdmi_depth_errors_space": (i32, [vp, i32, vp, i32, vp, i32, i64, f32, f32, vp, i32, f32, f32, vp, vp, vp]),
     "rdmi_depth_temporal": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, f32, f32, vp,
                                   vp, vp]),
+    "rdmi_select_bins": (i32, []),
+    "rdmi_select_passes": (i32, []),
+    "rdmi_select_state_bytes": (i64, []),
+    "rdmi_quantiles_workspace": (i64, []),
+    "rdmi_select_hist": (i32, [vp, i32, vp, i64, vp, i32, i32, vp, vp]),
+    "rdmi_select_pick": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "rdmi_quantiles": (i32, [vp, i32, vp, i64, vp, i32, vp, vp, vp]),
+    "rdmi_renormalize_clip_f32": (i32, [vp, i64, vp, vp]),
 }
 
 RDMI_F16, RDMI_F32, RDMI_U8, RDMI_F32_X3, RDMI_F32_X6 = 0, 1, 2, 3, 4

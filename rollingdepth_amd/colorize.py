@@ -89,14 +89,27 @@ def colorize_depth(depth: Union[np.ndarray, torch.Tensor], min_depth: float, max
 
 def colorize_depth_multi_thread(depth: Union[np.ndarray, torch.Tensor], valid_mask: Optional[np.ndarray] = None,
                                 chunk_size: int = 4, num_threads: int = 4, color_map: str = "Spectral",
-                                verbose: bool = False, device="cuda") -> np.ndarray:
+                                verbose: bool = False, device="cuda", percentiles=None) -> np.ndarray:
     """colorize.py:41-93: depth [N, 1, H, W] → uint8 [N, H, W, 3], normalised by the min / max over the
     valid pixels (all pixels without a mask).  chunk_size / num_threads / verbose are accepted for the
-    reference's signature; the whole video is one device launch."""
+    reference's signature; the whole video is one device launch.
+    `percentiles` (the build's own, None | (lo, hi) with 0 ≤ lo < hi ≤ 100, checked as forward()'s
+    renorm_percentiles): the normalisation bounds are the exact lo-th and hi-th percentiles of the valid pixels
+    (kernels.quantiles on the device, the mask included) instead of their min / max, so that a few stray pixels
+    do not take up the colormap; pixels outside the bounds get the colormap's end entries (the kernel clips)."""
+    if percentiles is not None:
+        from .pipeline import check_renorm_percentiles
+        percentiles = check_renorm_percentiles(percentiles)
     d = _as_device(depth, device).squeeze(1)
     assert d.dim() == 3
     nt = _np_dtype(d)
-    if valid_mask is None:
+    if percentiles is not None:
+        m = None
+        if valid_mask is not None:
+            m = torch.from_numpy(np.ascontiguousarray(np.asarray(valid_mask).reshape(d.shape).astype(bool))).to(d.device)
+        lohi = K.quantiles(d, [percentiles[0] / 100.0, percentiles[1] / 100.0], mask=m)
+        mn, mx = (nt(v) for v in lohi.tolist())  # exact: order statistics are values of the depth dtype
+    elif valid_mask is None:
         mn, mx = (nt(v) for v in K.minmax(d).tolist())  # exact: min / max are values of the depth dtype
     else:  # the reference reduces the masked pixels with numpy on the host (colorize.py:54-59)
         v = d.cpu().numpy()[np.asarray(valid_mask).reshape(d.shape).astype(bool)]

@@ -1339,6 +1339,127 @@ def scale_spread_(x: torch.Tensor, mm: torch.Tensor) -> torch.Tensor:
     return x
 
 
+# ----------------------------------------------------------------------------- exact quantiles (radix select)
+SELECT_MAX = 4  # RDMI_SELECT_MAX
+_Q_CACHE: dict = {}
+
+
+def select_bins() -> int:
+    return lib.rdmi_select_bins()
+
+
+def select_passes() -> int:
+    return lib.rdmi_select_passes()
+
+
+def _check_q(q, what: str) -> Tuple[float, ...]:
+    if isinstance(q, (str, bytes, torch.Tensor)) or not hasattr(q, "__len__"):
+        raise TypeError(f"{what}: q must be a sequence of 1 … {SELECT_MAX} Python floats, got {type(q).__name__}")
+    if not 1 <= len(q) <= SELECT_MAX:
+        raise ValueError(f"{what}: {len(q)} quantiles (1 … {SELECT_MAX})")
+    for v in q:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError(f"{what}: quantile fractions must be real numbers in [0, 1], got {list(q)}")
+    return tuple(float(v) for v in q)
+
+
+def _check_select_input(x: torch.Tensor, mask: Optional[torch.Tensor], what: str):
+    if x.dtype not in (F16, F32):
+        raise TypeError(f"{what}: f16/f32 expected, got {x.dtype}")
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{what}: mask must be bool or uint8, got {mask.dtype}")
+        if tuple(mask.shape) != tuple(x.shape):
+            raise ValueError(f"{what}: mask shape {tuple(mask.shape)} vs x {tuple(x.shape)}")
+        if mask.device != x.device:
+            raise ValueError(f"{what}: mask on {mask.device}, x on {x.device}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: expected a device tensor, got {x.device}")
+
+
+def _mask_u8(mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if mask is None:
+        return None
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def select_q(q: Sequence[float], device) -> torch.Tensor:
+    """The fractions as the f64 device tensor the pick step reads (kept per device and value)."""
+    q = _check_q(q, "select_q")
+    key = (str(device), q)
+    t = _Q_CACHE.get(key)
+    if t is None:
+        t = _Q_CACHE[key] = torch.tensor(q, dtype=torch.float64, device=device)
+    return t
+
+
+def select_state(device) -> torch.Tensor:
+    """Device memory for the state the passes of one select share (rdmi_select_pick's pass 0 fills it)."""
+    return torch.empty((lib.rdmi_select_state_bytes() + 7) // 8, dtype=torch.int64, device=device)
+
+
+def select_hist(x: torch.Tensor, state: torch.Tensor, pass_: int, k: int, hist: torch.Tensor,
+                mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One counting pass of the radix select over x (f16/f32, any shape; optional bool/uint8 mask of x's shape):
+    ADDS to hist (int64 [k, select_bins()], zeroed by the caller) pass `pass_`'s digit counts of the kept, non-NaN
+    elements that match each quantile's prefix in `state`.  The split form of quantiles(): histograms of several
+    chunks or ranks are summed before select_pick.  An empty x adds nothing."""
+    _check_select_input(x, mask, "select_hist")
+    _need(hist, torch.int64, "select_hist.hist")
+    if not 1 <= k <= SELECT_MAX or tuple(hist.shape) != (k, select_bins()) or not hist.is_contiguous():
+        raise ValueError(f"select_hist: hist {tuple(hist.shape)} for k = {k} (contiguous [k, {select_bins()}])")
+    if x.numel() == 0:
+        return hist
+    x, m = x.contiguous(), _mask_u8(mask)
+    check(lib.rdmi_select_hist(x.data_ptr(), int(x.dtype == F32), _p(m), x.numel(), state.data_ptr(), int(pass_), k,
+                               hist.data_ptr(), _stream()), "rdmi_select_hist")
+    return hist
+
+
+def select_pick(hist: torch.Tensor, q: torch.Tensor, pass_: int, k: int, state: torch.Tensor,
+                out: torch.Tensor) -> torch.Tensor:
+    """The pick step after pass `pass_`: extends each quantile's prefix in `state` by the bin of `hist` that holds
+    its rank; the last pass writes the k values to out (f32 [k]).  q: select_q()'s f64 device tensor."""
+    _need(hist, torch.int64, "select_pick.hist")
+    _need(q, torch.float64, "select_pick.q")
+    _need(out, F32, "select_pick.out")
+    if not 1 <= k <= SELECT_MAX or tuple(hist.shape) != (k, select_bins()) or q.numel() != k or out.numel() != k:
+        raise ValueError(f"select_pick: hist {tuple(hist.shape)}, {q.numel()} fractions, out {out.numel()} for k = {k}")
+    check(lib.rdmi_select_pick(hist.data_ptr(), q.data_ptr(), int(pass_), k, state.data_ptr(), out.data_ptr(),
+                               _stream()), "rdmi_select_pick")
+    return out
+
+
+def quantiles(x: torch.Tensor, q: Sequence[float], mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact order statistics of x on the device → f32 [len(q)] device tensor, no host sync.
+    x: f16/f32 of any shape (made contiguous).  q: 1 … 4 Python floats in [0, 1]; entry i is the data value of
+    0-based rank floor(q[i] · (cnt − 1)) among the cnt kept values — no interpolation, numpy's method="lower"
+    whenever both rank formulas are exact; NaN when nothing is kept.  mask: bool/uint8 of x's shape on x's device,
+    nonzero = keep.  NaNs are skipped, −0 counts as +0, ±inf are ordered like any value.  A radix select: the data
+    is read select_passes() times for all quantiles together, nothing is sorted or copied."""
+    q = _check_q(q, "quantiles")
+    _check_select_input(x, mask, "quantiles")
+    out = torch.empty(len(q), dtype=F32, device=x.device)
+    if x.numel() == 0:
+        return out.fill_(float("nan"))
+    x, m = x.contiguous(), _mask_u8(mask)
+    ws = _workspace((lib.rdmi_quantiles_workspace() + 3) // 4, x.device)
+    with _Timed("quantiles", 0, nbytes=select_passes() * x.numel() * (x.element_size() + (m is not None))):
+        check(lib.rdmi_quantiles(x.data_ptr(), int(x.dtype == F32), _p(m), x.numel(), select_q(q, x.device).data_ptr(),
+                                 len(q), out.data_ptr(), ws.data_ptr(), _stream()), "rdmi_quantiles")
+    return out
+
+
+def renormalize_clip_(x: torch.Tensor, lohi: torch.Tensor) -> torch.Tensor:
+    """In place renormalize_ with [lo, hi] = lohi on the device, then clamped to [−1, 1] (a NaN stays NaN).  With
+    lohi = minmax(x) the clamp never fires: bitwise renormalize_."""
+    _need(x, F32, "renormalize_clip.x")
+    _need(lohi, F32, "renormalize_clip.lohi")
+    check(lib.rdmi_renormalize_clip_f32(x.data_ptr(), x.numel(), lohi.data_ptr(), _stream()), "rdmi_renormalize_clip")
+    return x
+
+
 # ----------------------------------------------------------------------------- frame ingest / resize
 _RESIZE_MODES = {"NEAREST": _N.RDMI_RESIZE_NEAREST, "BILINEAR": _N.RDMI_RESIZE_BILINEAR,
                  "BICUBIC": _N.RDMI_RESIZE_BICUBIC}

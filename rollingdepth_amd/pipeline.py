@@ -192,6 +192,19 @@ def check_merge(merge) -> str:
     return merge
 
 
+def check_renorm_percentiles(renorm_percentiles) -> Optional[Tuple[float, float]]:
+    """`renorm_percentiles` must be None or (lo, hi), real numbers with 0 ≤ lo < hi ≤ 100 (bools are not
+    numbers here): ValueError otherwise, before any device work.  Returns None or the pair as floats."""
+    if renorm_percentiles is None:
+        return None
+    p = renorm_percentiles
+    ok = isinstance(p, (tuple, list)) and len(p) == 2 and all(
+        not isinstance(v, bool) and isinstance(v, numbers.Real) for v in p)
+    if not ok or not 0.0 <= p[0] < p[1] <= 100.0:
+        raise ValueError(f"renorm_percentiles must be None or (lo, hi) with 0 <= lo < hi <= 100, got {p!r}")
+    return float(p[0]), float(p[1])
+
+
 class RollingDepthPipeline:
     rgb_latent_scale_factor = 0.18215
     depth_latent_scale_factor = 0.18215
@@ -587,17 +600,20 @@ class RollingDepthPipeline:
                  refine_start_dilation: int = 6, generator: Union[torch.Generator, None] = None,
                  verbose: bool = False, max_vae_bs: int = 4, unload_snippet: bool = False,
                  restore_res: bool = False, input_fg_video_path=None, refine_stride: int = 1,
-                 output_uncertainty: bool = False, merge: str = "mean", **kw) -> RollingDepthOutput:
+                 output_uncertainty: bool = False, merge: str = "mean",
+                 renorm_percentiles: Optional[Tuple[float, float]] = None, **kw) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:78-176.  `input_video_path` (or the fork's `input_fg_video_path`):
         a video file (decoding needs PyAV, absent from this image), decoded uint8 rgb24 frames
         [N, H, W, 3] (numpy / torch: resized to processing_res and normalised on the device,
         video_io.load_video_frames), or an already-normalised float [N, 3, H, W] tensor in [-1, 1]
         (used as is: processing_res and restore_res do not apply to it).  `refine_stride` (the build's own,
-        1 … refine_snippet_len), `output_uncertainty` and `merge` ("mean" | "median"): see forward().
+        1 … refine_snippet_len), `output_uncertainty`, `merge` ("mean" | "median") and `renorm_percentiles`
+        (None | (lo, hi)): see forward().
         restore_res resizes depth_uncertainty as it resizes depth_pred."""
         check_refine_stride(refine_stride, refine_snippet_len)
         check_output_uncertainty(output_uncertainty)
         check_merge(merge)
+        check_renorm_percentiles(renorm_percentiles)
         assert processing_res >= 0
         if processing_res > 1024:
             logging.warning(f"Procssing at high-resolution ({processing_res}) may lead to suboptimal accuracy.")
@@ -621,7 +637,9 @@ class RollingDepthPipeline:
                            init_infer_steps, strides, coalign_kwargs, refine_step, refine_snippet_len,
                            refine_start_dilation, generator, verbose, max_vae_bs, unload_snippet,
                            refine_stride=refine_stride, output_uncertainty=output_uncertainty,
-                           **(dict(merge=merge) if merge != "mean" else {}), **kw)
+                           **(dict(merge=merge) if merge != "mean" else {}),
+                           **(dict(renorm_percentiles=renorm_percentiles) if renorm_percentiles is not None else {}),
+                           **kw)
         if restore_res:  # rollingdepth_pipeline.py:155-173 (torchvision resize, antialias=True), on the device
             for name in ("input_rgb", "depth_pred") + (("depth_uncertainty",) if output_uncertainty else ()):
                 t = getattr(out, name)
@@ -635,7 +653,8 @@ class RollingDepthPipeline:
 
     def _forward_sharded(self, input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs, refine_step,
                          refine_snippet_len, refine_start_dilation, init_noise, record, generator=None, strides=1,
-                         refine_stride: int = 1, output_uncertainty: bool = False, merge: str = "mean"):
+                         refine_stride: int = 1, output_uncertainty: bool = False, merge: str = "mean",
+                         renorm_percentiles: Optional[Tuple[float, float]] = None):
         """forward() over W ranks (shard.sharded_forward), outputs assembled on every rank.  Dilations
         arrive already capped and strides validated (forward's checks ran); the snippets are all-gathered
         at full resolution only here, to honour the snippet_ls contract (bench.py keeps them distributed)."""
@@ -649,7 +668,8 @@ class RollingDepthPipeline:
                              gather=True, record=record, generator=generator,
                              init_infer_steps=list(init_infer_steps),
                              strides=list(strides) if isinstance(strides, (list, tuple)) else strides,
-                             refine_stride=refine_stride, output_uncertainty=output_uncertainty, merge=merge)
+                             refine_stride=refine_stride, output_uncertainty=output_uncertainty, merge=merge,
+                             renorm_percentiles=renorm_percentiles)
         snips = gather_rows_by_dilation([r.to(self.dtype) for r in so.snippet_rows], so.snippet_counts, world,
                                         self._group)
         H, W = so.depth_pred_full.shape[-2:]
@@ -669,7 +689,8 @@ class RollingDepthPipeline:
                 refine_start_dilation: int, generator: Union[torch.Generator, None], verbose: bool,
                 max_vae_bs: int, unload_snippet: bool, init_noise: Optional[torch.Tensor] = None,
                 record: Optional[dict] = None, refine_stride: int = 1,
-                output_uncertainty: bool = False, merge: str = "mean") -> RollingDepthOutput:
+                output_uncertainty: bool = False, merge: str = "mean",
+                renorm_percentiles: Optional[Tuple[float, float]] = None) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:193-353.  `refine_stride` (the build's own, 1 … refine_snippet_len):
         each refine step starts its snippets that many positions apart inside every residue class mod the
         step's dilation (refine_snippet_indice), so a frame passes the UNet about refine_snippet_len /
@@ -683,10 +704,21 @@ class RollingDepthPipeline:
         per-pixel median (the mean of the two middle ones for an even count), which one badly aligned snippet
         cannot move; depth_coaligned is then the renormalised median map, the refine stage starts from it, and
         depth_uncertainty is the predictions' median absolute deviation around it — the raw MAD, no 1.4826
-        factor — scaled like the standard deviation.  snippet_ls is untouched."""
+        factor — scaled like the standard deviation.  snippet_ls is untouched.
+        `renorm_percentiles` (the build's own, None | (lo, hi) with 0 ≤ lo < hi ≤ 100; anything else is a
+        ValueError): the range the merged map is renormalised with.  None is the reference's global min / max.
+        With (lo, hi) the range is [v_lo, v_hi], the merged video's exact lo-th and hi-th percentiles (the data
+        values of 0-based rank floor(p/100 · (count − 1)), kernels.quantiles — no interpolation), so that a few
+        stray pixels no longer set the scale of every other one: v_lo maps to −1, v_hi to +1 and what lies
+        outside is clipped to ±1.  depth_coaligned is the clipped map, the refine stage starts from it,
+        depth_uncertainty is scaled by the same range (2 / (v_hi − v_lo): still depth_coaligned's units, not
+        clipped), snippet_ls is untouched.  (0, 100) reproduces None bitwise.  A degenerate range, v_hi == v_lo
+        — a map constant between the two percentiles — divides by zero as a constant map does in the reference:
+        pixels equal to v_lo become NaN, the others ±1; no host sync is spent on detecting it."""
         refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
         check_output_uncertainty(output_uncertainty)
         check_merge(merge)
+        renorm_percentiles = check_renorm_percentiles(renorm_percentiles)
         # ----------------- checks (rollingdepth_pipeline.py:214-252)
         assert 1 in dilations, "dilations should include 1"
         assert len(snippet_lengths) == len(set(snippet_lengths)), f"Repeated values found in {snippet_lengths = }"
@@ -738,7 +770,8 @@ class RollingDepthPipeline:
             if dist.get_world_size(self._group) > 1:
                 return self._forward_sharded(input_frames, dilations, snippet_lengths, init_infer_steps, coalign_kwargs,
                                              refine_step, refine_snippet_len, refine_start_dilation, init_noise,
-                                             record, generator, strides, refine_stride, output_uncertainty, merge)
+                                             record, generator, strides, refine_stride, output_uncertainty, merge,
+                                             renorm_percentiles)
         # ----------------- encode (H2D boundary :263)
         frames = input_frames[0].to(self.device)
         # input_rgb = frames / 2 + 0.5 in f16 as the reference computes it on the host (x/2 is exact,
@@ -765,9 +798,13 @@ class RollingDepthPipeline:
             strides=strides if strided else None, sequence_length=N if strided else None, merged_f32=self.merge_f32,
             uncertainty=output_uncertainty, **(dict(merge=merge) if merge != "mean" else {}))
         d = merged.float().contiguous()
-        mm = K.minmax(d)
-        K.renormalize_(d, mm)
-        if output_uncertainty:  # the spread in the renormalised map's units (mm: the merged map's min / max)
+        if renorm_percentiles is None:
+            mm = K.minmax(d)
+            K.renormalize_(d, mm)
+        else:  # the range between two exact percentiles of the merged video, the rest clipped to ±1
+            mm = K.quantiles(d, [renorm_percentiles[0] / 100.0, renorm_percentiles[1] / 100.0])
+            K.renormalize_clip_(d, mm)
+        if output_uncertainty:  # the spread in the renormalised map's units (mm: the merged map's min / max, or its percentile range)
             spread = K.scale_spread_(spread[0].contiguous(), mm)
         coaligned = d.to(self.dtype)
         _progress("co-alignment done")

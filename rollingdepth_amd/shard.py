@@ -222,6 +222,24 @@ def _all_reduce_minmax(mm: torch.Tensor, group=None) -> torch.Tensor:
     return torch.stack([t[0], -t[1]])
 
 
+def _all_reduce_quantiles(d: torch.Tensor, q: Sequence[float], group=None) -> torch.Tensor:
+    """kernels.quantiles of the ranks' chunks taken together → f32 [len(q)], identical on every rank: per pass
+    of the radix select each rank histograms its own chunk `d` (an empty chunk contributes zeros and still joins),
+    one all-reduce SUM of the int64 [k, bins] histogram, then every rank runs the same pick.  Integer sums: bitwise
+    the single-GPU values."""
+    from . import kernels as K
+
+    dev, k = d.device, len(q)
+    qd, state = K.select_q(q, dev), K.select_state(dev)
+    out = torch.empty(k, dtype=F32, device=dev)
+    for p in range(K.select_passes()):
+        hist = torch.zeros((k, K.select_bins()), dtype=torch.int64, device=dev)
+        K.select_hist(d, state, p, k, hist)
+        _all_reduce(hist, group=group)
+        K.select_pick(hist, qd, p, k, state, out)
+    return out
+
+
 def _strided(start_steps: Optional[Sequence[int]]) -> bool:
     return start_steps is not None and any(int(s) != 1 for s in start_steps)
 
@@ -478,7 +496,8 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
                     generator: Optional[torch.Generator] = None,
                     init_infer_steps: Union[int, Sequence[int]] = 1, timing: Optional[list] = None,
                     strides: Union[int, Sequence[int]] = 1, refine_stride: int = 1,
-                    output_uncertainty: bool = False, merge: str = "mean") -> ShardedOutput:
+                    output_uncertainty: bool = False, merge: str = "mean",
+                    renorm_percentiles: Optional[Tuple[float, float]] = None) -> ShardedOutput:
     """Multi-GPU RollingDepthPipeline.forward (every preset: refine_step > 0 included).
 
     `input_frames` is either the whole video [1,N,3,H,W] / [N,3,H,W], or — with `num_frames=N` —
@@ -503,14 +522,18 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
     `gather`; to_host copies it as the other maps.
     `merge`: forward()'s ("mean" | "median").  Under "median" the windowed merge exchanges the covering terms
     themselves (terms_exchange_plan) and each owner takes the per-pixel median of its frames' terms, bitwise
-    the single-GPU median merge; depth_uncertainty is then their raw MAD (no 1.4826 factor)."""
+    the single-GPU median merge; depth_uncertainty is then their raw MAD (no 1.4826 factor).
+    `renorm_percentiles`: forward()'s (None | (lo, hi)).  With a pair the renormalisation range is the two exact
+    percentiles of the whole merged video: per pass of the radix select one all-reduce SUM of the ranks' int64
+    histograms (_all_reduce_quantiles) in place of the min / max all-reduce — bitwise the single-GPU range."""
     from . import kernels as K
     from .aligner import DepthAligner, check_row_layout, snippet_count, snippet_last, snippet_start
-    from .pipeline import check_merge, check_output_uncertainty, check_refine_stride
+    from .pipeline import check_merge, check_output_uncertainty, check_refine_stride, check_renorm_percentiles
 
     refine_stride = check_refine_stride(refine_stride, refine_snippet_len)
     check_output_uncertainty(output_uncertainty)
     check_merge(merge)
+    renorm_percentiles = check_renorm_percentiles(renorm_percentiles)
 
     if group is None:
         group = dist.group.WORLD
@@ -612,10 +635,15 @@ def sharded_forward(pipe, input_frames: torch.Tensor, dilations: List[int], cap_
         merged, spread = merged
     # merge_scaled_triplets returns the snippets' dtype (unless the pipeline merges in f32)
     d = (merged if (pipe.merge_f32 or rows_f32) else merged.to(pipe.dtype).float()).contiguous()
-    mm_d = K.minmax(d) if d.numel() else torch.tensor([float("inf"), float("-inf")], device=dev)
-    gmm = _all_reduce_minmax(mm_d, group)
-    if d.numel():
-        K.renormalize_(d, gmm)
+    if renorm_percentiles is None:
+        mm_d = K.minmax(d) if d.numel() else torch.tensor([float("inf"), float("-inf")], device=dev)
+        gmm = _all_reduce_minmax(mm_d, group)
+        if d.numel():
+            K.renormalize_(d, gmm)
+    else:
+        gmm = _all_reduce_quantiles(d, [renorm_percentiles[0] / 100.0, renorm_percentiles[1] / 100.0], group)
+        if d.numel():
+            K.renormalize_clip_(d, gmm)
     if output_uncertainty:
         if spread.numel():
             K.scale_spread_(spread, gmm)
