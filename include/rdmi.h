@@ -649,6 +649,76 @@ int rdmi_quantiles(const void* x, int x_f32, const unsigned char* mask, long n, 
  * elements equal to lo become NaN, the others ±1. */
 int rdmi_renormalize_clip_f32(float* x, long n, const float* lohi, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Optical flow (since rdmi_version 10): a classical, deterministic, dense pyramidal Lucas–Kanade estimator with
+ * template gradients, and a forward–backward consistency check — the flow and the occlusion mask that
+ * rdmi_depth_temporal's `flow` and `pair_mask` arguments were made for, from nothing but the RGB frames.  An
+ * evaluation instrument: exact to the specification below, bit for bit reproducible, no learned part.  The
+ * reference has no counterpart.  All arithmetic is f32, each operation rounded once or contracted to an fma.
+ *
+ * Luma.  Y = 0.299 R + 0.587 G + 0.114 B of frames given by a base pointer, a dtype (RDMI_F16, RDMI_F32, RDMI_U8) and
+ *   four ELEMENT strides (frame, channel, row, column): [N, 3, H, W] floats, [N, H, W, 3] bytes and any strided or
+ *   offset view of either are the same call.  Any affine range of the values gives the same flow (up to the 1e-12
+ *   below).
+ * Pyramid.  Level 0 is the luma; level l + 1 has ⌈H_l / 2⌉ × ⌈W_l / 2⌉ pixels, each ¼ · ((a + b) + (c + d)) of the
+ *   2 × 2 block at (2y, 2x), indices clamped to the image.  The level rule: with s = 4 · (2r + 1), level l exists
+ *   while l < 5 and (l = 0 or min(H_l, W_l) ≥ s); rdmi_flow_levels clamps a request of `levels` ≥ 1 to that count,
+ *   ≤ 0 asks for it.  The other calls take 1 … RDMI_FLOW_MAX_LEVELS levels as given (a level deeper than the rule's
+ *   only has more truncated windows) and read ≤ 0 (rdmi_flow_estimate, rdmi_flow_workspace) as the rule's count;
+ *   the Python surface clamps a caller's request by the rule first.  pyr holds the levels one after the other: level l is [N][H_l][W_l] at the offset Σ_{j<l} N·H_j·W_j floats.
+ * One level, pixel p = (x, y), radius r, window = the (2r + 1)² taps q = p + (i, j), |i|, |j| ≤ r, in row-major
+ *   order (j outer), of which only those inside the image count:
+ *     Ix(q) = ½ · (I0(qx + 1, qy) − I0(qx − 1, qy)), Iy alike, neighbour indices clamped to the image;
+ *     Axx = Σ Ix², Axy = Σ Ix·Iy, Ayy = Σ Iy²;  λ = damping · (½ · (Axx + Ayy)) + 1e-12;
+ *     a11 = Axx + λ, a22 = Ayy + λ, det = a11·a22 − Axy²;
+ *   u(p) starts at 0 on the coarsest level and else at 2 · the coarse flow sampled bilinearly at
+ *   ((x + ½)/2 − ½, (y + ½)/2 − ½), clamped to the coarse image; then `iterations` times
+ *     b = Σ_q ∇I0(q) · (I1(q + u(p)) − I0(q)), with X = min(max(qx + ux, 0), W − 1), Y alike, x0 = ⌊X⌋, wx = X − x0,
+ *       x1 = min(x0 + 1, W − 1), and I1(X, Y) = (1 − wy)·((1 − wx)·I00 + wx·I01) + wy·((1 − wx)·I10 + wx·I11);
+ *     du = (−(a22·bx − Axy·by) / det, −(a11·by − Axy·bx) / det); where |du| > 1, du ← du / |du|;  u ← u + du.
+ *   max / min return the other operand for a NaN, so no address is formed outside the image whatever the frames
+ *   hold.  The flow of p moves the whole window of p: a pixel never reads a neighbour's flow within a level, its
+ *   sums run in one lane in the fixed order above, and nothing is atomic — the same frames give the same bits,
+ *   for a pair alone or in a batch, forward or as the backward flow of the reversed video.
+ * Flow.  f32 [pairs][H][W][2] = (dx, dy) in pixels from frame i to frame i + k, rdmi_depth_temporal's convention.
+ * Forward–backward check.  valid [pairs][H][W] (u8, 1 / 0): with X = x + uf.x, Y = y + uf.y, pixel p is valid iff
+ *   0 ≤ X ≤ W − 1 and 0 ≤ Y ≤ H − 1 and, for ub = the backward flow sampled bilinearly at (X, Y) (formula above),
+ *   |uf + ub|² ≤ α · (|uf|² + |ub|²) + β.  A NaN anywhere fails the tests: invalid.
+ *
+ * rdmi_flow_levels: the level rule (host arithmetic only; 0 for H, W < 1 or r outside 1 … 7).
+ * rdmi_flow_workspace: bytes rdmi_flow_estimate needs (0 for arguments it would refuse): the pyramid of all N
+ *   frames and, per direction, the flows of the levels above 0.
+ * rdmi_flow_pyramid: luma and every level of all N frames into pyr (f32, 4-byte aligned), 1 + (levels − 1) launches.
+ * rdmi_flow_lk_level: one level, one direction, all pairs in ONE launch: pair i takes frame first0 + i of img
+ *   [N][Hl][Wl] as I0 and frame first1 + i as I1 (forward: 0 and k; backward: k and 0), starts from `coarse`
+ *   [pairs][Hc][Wc][2] (NULL: zero; else Hc = ⌈Hl/2⌉, Wc = ⌈Wl/2⌉ is required) and writes flow [pairs][Hl][Wl][2].
+ *   A workgroup owns a 32 × 8 pixel tile of one pair, stages I0 with an r + 1 halo in LDS, derives Ix, Iy there,
+ *   and each lane then runs all iterations in registers; I1 is read through the caches.
+ * rdmi_flow_fb_check: the check above, one launch.
+ * rdmi_flow_estimate: pyramid, then per level from the coarsest the forward and (backward ≠ 0) the backward launch,
+ *   then the check, on one stream.  flow_bwd and valid are written only when backward ≠ 0.
+ * RDMI_E_ARG before any launch: a null frames / pyr / img / flow / fwd / bwd / valid / workspace (flow_bwd and valid
+ *   only when backward ≠ 0), N < 1 (rdmi_flow_estimate: N < 2), H, W, pairs or iterations < 1, frame_step < 1 or ≥ N,
+ *   first0 / first1 < 0 or + pairs > N, r outside 1 … 7, levels outside 1 … RDMI_FLOW_MAX_LEVELS (pyramid; estimate: above it), a dtype
+ *   outside the three, a coarse size other than the halved one, damping < 0 or NaN, α or β < 0 or NaN.
+ * RDMI_E_ALIGN: pyr / img not 4-byte, flow / coarse / fwd / bwd not 8-byte, workspace not 16-byte aligned.
+ * RDMI_E_UNSUPPORTED: H·W > 2^30 or more than 65535 pairs.  Frame bases are 64-bit: N·H·W is not limited. */
+#define RDMI_FLOW_MAX_LEVELS 5
+#define RDMI_FLOW_MAX_RADIUS 7
+int rdmi_flow_levels(int H, int W, int radius, int levels);
+long rdmi_flow_workspace(int N, int H, int W, int frame_step, int radius, int levels, int backward);
+int rdmi_flow_pyramid(const void* frames, int dtype, long stride_n, long stride_c, long stride_y, long stride_x, int N,
+                      int H, int W, int levels, float* pyr, void* stream);
+int rdmi_flow_lk_level(const float* img, int N, int Hl, int Wl, int first0, int first1, int pairs,
+                       const float* coarse, int Hc, int Wc, float* flow, int radius, int iterations, float damping,
+                       void* stream);
+int rdmi_flow_fb_check(const float* fwd, const float* bwd, int pairs, int H, int W, float alpha, float beta,
+                       unsigned char* valid, void* stream);
+int rdmi_flow_estimate(const void* frames, int dtype, long stride_n, long stride_c, long stride_y, long stride_x,
+                       int N, int H, int W, int frame_step, int levels, int radius, int iterations, float damping,
+                       int backward, float alpha, float beta, float* flow, float* flow_bwd, unsigned char* valid,
+                       void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

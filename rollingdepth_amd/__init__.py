@@ -4,7 +4,8 @@ Public surface mirrors the reference: RollingDepthPipeline / RollingDepthOutput
 (rollingdepth/rollingdepth_pipeline.py), DepthAligner (rollingdepth/depth_aligner.py) and the
 modified diffusers attention processor (CrossFrameAttnProcessor); depth_metrics / align_scale_shift
 (metrics.py) score a depth video after a least-squares scale and shift, temporal_metrics its change
-from frame to frame; quantiles (kernels.py) takes exact order statistics of a device tensor.  All arithmetic runs in
+from frame to frame, optical_flow (flow.py) estimates the flow and occlusion mask that score needs from the
+RGB frames; quantiles (kernels.py) takes exact order statistics of a device tensor.  All arithmetic runs in
 librdmi.so (HIP); importing the compute modules without the built library raises.
 """
 __version__ = "0.1.0"
@@ -23,6 +24,9 @@ def __getattr__(name):
     if name in ("depth_metrics", "align_scale_shift", "DepthMetrics", "temporal_metrics", "TemporalMetrics"):
         from . import metrics
         return getattr(metrics, name)
+    if name in ("optical_flow", "OpticalFlow"):
+        from . import flow
+        return getattr(flow, name)
     if name == "quantiles":
         from .kernels import quantiles
         return quantiles

@@ -154,6 +154,13 @@ _SIGS = {
     "rdmi_select_pick": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "rdmi_quantiles": (i32, [vp, i32, vp, i64, vp, i32, vp, vp, vp]),
     "rdmi_renormalize_clip_f32": (i32, [vp, i64, vp, vp]),
+    "rdmi_flow_levels": (i32, [i32, i32, i32, i32]),
+    "rdmi_flow_workspace": (i64, [i32, i32, i32, i32, i32, i32, i32]),
+    "rdmi_flow_pyramid": (i32, [vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp]),
+    "rdmi_flow_lk_level": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, f32, vp]),
+    "rdmi_flow_fb_check": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp]),
+    "rdmi_flow_estimate": (i32, [vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, f32, i32, f32, f32,
+                                 vp, vp, vp, vp, vp]),
 }
 
 RDMI_F16, RDMI_F32, RDMI_U8, RDMI_F32_X3, RDMI_F32_X6 = 0, 1, 2, 3, 4

@@ -1618,3 +1618,121 @@ def depth_temporal(pred: torch.Tensor, target: Optional[torch.Tensor], mask: Opt
                                   N, H, W, frame_step, lo, hi, st.data_ptr(), space, clip_lo, clip_hi, ws.data_ptr(),
                                   sums.data_ptr(), _stream()), "rdmi_depth_temporal")
     return sums
+
+
+# ----------------------------------------------------------------------------- optical flow (pyramidal Lucas–Kanade)
+FLOW_MAX_LEVELS, FLOW_MAX_RADIUS = 5, 7  # RDMI_FLOW_MAX_LEVELS, RDMI_FLOW_MAX_RADIUS
+
+
+def flow_levels(H: int, W: int, radius: int = 5, levels: Optional[int] = None) -> int:
+    """The pyramid's level count by librdmi's own rule (rdmi.h "Optical flow"): as many levels as keep the smaller
+    side at 4·(2·radius + 1) pixels or more, at most 5, at least 1; a request `levels` is clamped to that.  Host
+    arithmetic only.  0 for sizes below 1 or a radius outside 1 … 7."""
+    return lib.rdmi_flow_levels(int(H), int(W), int(radius), 0 if levels is None else int(levels))
+
+
+def flow_level_sizes(H: int, W: int, levels: int):
+    """[(H_l, W_l)] of the pyramid: each level ⌈·/2⌉ of the one before."""
+    out = []
+    for _ in range(levels):
+        out.append((H, W))
+        H, W = (H + 1) // 2, (W + 1) // 2
+    return out
+
+
+def _flow_frames(frames: torch.Tensor, what: str):
+    """→ (dtype code, N, H, W, element strides n, c, y, x) of [N, 3, H, W] f16 / f32 or [N, H, W, 3] uint8 frames;
+    any strided view is taken as it is, nothing is copied."""
+    if not frames.is_cuda:
+        raise ValueError(f"{what}: expected a device tensor, got {frames.device}")
+    if frames.dim() != 4:
+        raise ValueError(f"{what}: 4-D frames expected, got {tuple(frames.shape)}")
+    if frames.dtype == torch.uint8:
+        N, H, W, Cc = frames.shape
+        sn, sy, sx, sc = frames.stride()
+        code = _N.RDMI_U8
+    elif frames.dtype in (F16, F32):
+        N, Cc, H, W = frames.shape
+        sn, sc, sy, sx = frames.stride()
+        code = _dtype_code(frames)
+    else:
+        raise TypeError(f"{what}: f16 / f32 [N, 3, H, W] or uint8 [N, H, W, 3] expected, got {frames.dtype}")
+    if Cc != 3:
+        raise ValueError(f"{what}: three channels expected, got shape {tuple(frames.shape)}")
+    return code, N, H, W, sn, sc, sy, sx
+
+
+def flow_pyramid(frames: torch.Tensor, levels: int) -> list:
+    """Luma and its 2 × 2-mean pyramid of every frame → [f32 [N, H_l, W_l]] for l < levels, views of one buffer in
+    rdmi_flow_pyramid's layout (level after level)."""
+    code, N, H, W, sn, sc, sy, sx = _flow_frames(frames, "flow_pyramid")
+    sizes = flow_level_sizes(H, W, levels)
+    buf = torch.empty(max(sum(N * h * w for h, w in sizes), 1), dtype=F32, device=frames.device)
+    check(lib.rdmi_flow_pyramid(frames.data_ptr(), code, sn, sc, sy, sx, N, H, W, levels, buf.data_ptr(), _stream()),
+          "rdmi_flow_pyramid")
+    out, off = [], 0
+    for h, w in sizes:
+        out.append(buf[off:off + N * h * w].view(N, h, w))
+        off += N * h * w
+    return out
+
+
+def flow_lk_level(img: torch.Tensor, first0: int, first1: int, pairs: int, coarse: Optional[torch.Tensor] = None,
+                  radius: int = 5, iterations: int = 3, damping: float = 0.01) -> torch.Tensor:
+    """One Lucas–Kanade level, one direction, all pairs in one launch → f32 [pairs, H_l, W_l, 2].  img: a level of
+    flow_pyramid; pair i takes frame first0 + i as the template and frame first1 + i as the moving image; coarse: the
+    next-coarser level's flow [pairs, ⌈H_l/2⌉, ⌈W_l/2⌉, 2] or None (start from zero)."""
+    _need(img, F32, "flow_lk_level.img")
+    if img.dim() != 3 or not img.is_contiguous():
+        raise ValueError(f"flow_lk_level.img: contiguous [N, H, W] expected, got {tuple(img.shape)}")
+    N, H, W = img.shape
+    Hc = Wc = 0
+    if coarse is not None:
+        _need(coarse, F32, "flow_lk_level.coarse")
+        if coarse.dim() != 4 or coarse.shape[0] != pairs or coarse.shape[3] != 2 or not coarse.is_contiguous():
+            raise ValueError(f"flow_lk_level.coarse: contiguous [pairs, Hc, Wc, 2] expected, got {tuple(coarse.shape)}")
+        Hc, Wc = coarse.shape[1], coarse.shape[2]
+    flow = torch.empty((max(pairs, 0), H, W, 2), dtype=F32, device=img.device)
+    with _Timed("flow_lk_level", 0, shape=(pairs, H, W, radius, iterations)):
+        check(lib.rdmi_flow_lk_level(img.data_ptr(), N, H, W, first0, first1, pairs, _p(coarse), Hc, Wc,
+                                     flow.data_ptr(), radius, iterations, damping, _stream()), "rdmi_flow_lk_level")
+    return flow
+
+
+def flow_fb_check(fwd: torch.Tensor, bwd: torch.Tensor, alpha: float = 0.01, beta: float = 0.5) -> torch.Tensor:
+    """Forward–backward consistency of two flows f32 [pairs, H, W, 2] → uint8 [pairs, H, W], 1 = consistent and the
+    target inside the frame."""
+    _need(fwd, F32, "flow_fb_check.fwd")
+    _need(bwd, F32, "flow_fb_check.bwd")
+    if fwd.dim() != 4 or fwd.shape[3] != 2 or bwd.shape != fwd.shape or not (fwd.is_contiguous() and bwd.is_contiguous()):
+        raise ValueError(f"flow_fb_check: two contiguous [pairs, H, W, 2] flows expected, got {tuple(fwd.shape)} and "
+                         f"{tuple(bwd.shape)}")
+    pairs, H, W, _ = fwd.shape
+    valid = torch.empty((pairs, H, W), dtype=torch.uint8, device=fwd.device)
+    check(lib.rdmi_flow_fb_check(fwd.data_ptr(), bwd.data_ptr(), pairs, H, W, alpha, beta, valid.data_ptr(),
+                                 _stream()), "rdmi_flow_fb_check")
+    return valid
+
+
+def flow_estimate(frames: torch.Tensor, frame_step: int = 1, levels: Optional[int] = None, radius: int = 5,
+                  iterations: int = 3, damping: float = 0.01, backward: bool = True, alpha: float = 0.01,
+                  beta: float = 0.5):
+    """rdmi_flow_estimate, the whole chain on the current stream → (flow, flow_backward or None, valid or None).
+    levels None: the rule's count; a number is taken as given (1 … 5) — rollingdepth_amd.flow.optical_flow clamps
+    it by the rule first."""
+    code, N, H, W, sn, sc, sy, sx = _flow_frames(frames, "flow_estimate")
+    lv = 0 if levels is None else int(levels)
+    if levels is not None and not 1 <= lv <= FLOW_MAX_LEVELS:
+        raise ValueError(f"flow_estimate: levels {levels} outside 1 … {FLOW_MAX_LEVELS}")
+    pairs = max(N - frame_step, 0)
+    dev = frames.device
+    nbytes = lib.rdmi_flow_workspace(N, H, W, frame_step, radius, lv, int(backward))
+    ws = torch.empty(max(nbytes // 4, 4), dtype=F32, device=dev)
+    flow = torch.empty((pairs, H, W, 2), dtype=F32, device=dev)
+    bwd = torch.empty((pairs, H, W, 2), dtype=F32, device=dev) if backward else None
+    valid = torch.empty((pairs, H, W), dtype=torch.uint8, device=dev) if backward else None
+    with _Timed("flow_estimate", 0, shape=(N, H, W, frame_step, radius, iterations)):
+        check(lib.rdmi_flow_estimate(frames.data_ptr(), code, sn, sc, sy, sx, N, H, W, frame_step, lv, radius,
+                                     iterations, damping, int(backward), alpha, beta, flow.data_ptr(), _p(bwd),
+                                     _p(valid), ws.data_ptr(), _stream()), "rdmi_flow_estimate")
+    return flow, bwd, valid

@@ -12,9 +12,10 @@ frame, and reports AbsRel and δ < 1.25ᵏ on the valid pixels:
 The fit can also be taken in disparity or log-depth (space="disparity" | "log": against 1 / target or
 ln target, the aligned value brought back to depth before the errors), and temporal_metrics scores the change
 from frame to frame — flicker, and the temporal-gradient error against the target's own change — optionally
-along an optical flow the caller supplies:
+along an optical flow the caller supplies or that is estimated from the RGB frames (flow.py):
 
     t = temporal_metrics(pred, target, mask, flow=flow)   # flow [N − 1, H, W, 2], (dx, dy) in pixels
+    t = temporal_metrics(pred, target, mask, frames=rgb)  # flow and occlusion mask estimated from the frames
     t.flicker, t.tge, t.change_corr
 
 All sums run in librdmi (rdmi_depth_moments / _fit / _errors / _temporal, f64, fixed summation order: the same
@@ -239,7 +240,8 @@ def _pool_temporal(per_pair: torch.Tensor, scale: torch.Tensor, shift: torch.Ten
 def temporal_metrics(pred: torch.Tensor, target: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                      *, flow: Optional[torch.Tensor] = None, pair_mask: Optional[torch.Tensor] = None,
                      frame_step: int = 1, align: str = "video", space: str = "depth",
-                     valid_range=(1e-3, math.inf), clip: Optional[Tuple[float, float]] = None) -> TemporalMetrics:
+                     valid_range=(1e-3, math.inf), clip: Optional[Tuple[float, float]] = None,
+                     frames: Optional[torch.Tensor] = None) -> TemporalMetrics:
     """Temporal consistency of a depth video: the change of the aligned prediction a between frame i and frame
     i + frame_step (flicker) and its difference from the target's own change (temporal-gradient error).
 
@@ -249,9 +251,12 @@ def temporal_metrics(pred: torch.Tensor, target: Optional[torch.Tensor] = None, 
     are NaN.  flow: f32 [N − frame_step, H, W, 2], (dx, dy) in pixels from frame i to frame i + frame_step; the
     later frame is then sampled bilinearly at (x + dx, y + dy), and a pixel whose taps leave the frame or touch
     an invalid pixel is left out.  Without a flow the same pixel is compared — right for a static camera, an upper
-    bound on flicker otherwise; no flow estimator is part of this package.  pair_mask: bool / uint8
-    [N − frame_step, H, W], pixels of frame i to use in pair i (an occlusion mask).  With no valid pixel at all
-    every metric is NaN."""
+    bound on flicker otherwise.  pair_mask: bool / uint8 [N − frame_step, H, W], pixels of frame i to use in pair i
+    (an occlusion mask).  frames: the video's RGB frames ([N, 3, H, W] f16 / f32, or uint8 [N, H, W, 3], of pred's
+    N, H and W) in place of a flow: the flow and its forward–backward mask are then estimated at this call's
+    frame_step by rollingdepth_amd.flow.optical_flow with its defaults, the flow is used, and the mask is ANDed
+    into pair_mask; frames together with a flow is a ValueError.  With no valid pixel at all every metric is
+    NaN."""
     if align not in ALIGN_MODES:
         raise ValueError(f"align: one of {ALIGN_MODES} expected, got {align!r}")
     if target is None and align != "none":
@@ -267,9 +272,16 @@ def temporal_metrics(pred: torch.Tensor, target: Optional[torch.Tensor] = None, 
             raise TypeError(f"{name}: a tensor expected, got {type(t).__name__}")
         if t.dtype not in dtypes:
             raise TypeError(f"{name}: {what} expected, got {t.dtype}")
+    if frames is not None and flow is not None:
+        raise ValueError("frames: give the frames or a flow, not both (the flow would be estimated from the frames)")
 
     def pair_checks(shape):
         N, H, W = shape
+        if frames is not None:
+            from .flow import check_flow_args
+
+            if check_flow_args(frames, frame_step)[:3] != (N, H, W):
+                raise ValueError(f"frames: shape {tuple(frames.shape)} does not match pred's N, H, W = {(N, H, W)}")
         if not 1 <= frame_step < N:
             raise ValueError(f"frame_step: 1 <= frame_step < N = {N} expected, got {frame_step}")
         pairs = N - frame_step
@@ -292,6 +304,12 @@ def temporal_metrics(pred: torch.Tensor, target: Optional[torch.Tensor] = None, 
         pm = pair_mask.to(dev).contiguous().view(pairs, P)
         if pm.dtype == torch.bool:
             pm = pm.view(torch.uint8)
+    if frames is not None:
+        from .flow import optical_flow
+
+        est = optical_flow(frames.to(dev), frame_step)
+        fl, valid = est.flow, est.valid.view(pairs, P)
+        pm = valid if pm is None else ((pm != 0) & (valid != 0)).view(torch.uint8)
     sp = K.DEPTH_SPACES[space]
     ws = K.depth_metrics_workspace(N, P, dev)  # the moments' N rows; the temporal pass needs N − frame_step
     if align != "none":
