@@ -4,15 +4,16 @@
 // autograd, with three host syncs per iteration (loss.item(), summ.min/max, :213).  Here one
 // iteration is three kernels with no host involvement:
 //   frame_stats  — per frame f and subsampled pixel p, the mean over every covering (dilation,
-//                  slot) of A = x·s + t and of 1/clip(A, 1e-3) (the M / M_depth / B scatter and
-//                  the .sum(0)/B.sum(0) of :169-191, summed in the reference's row order), plus
+//                  slot) of A = x·s + t (one fma: rounded once, see mulrn below) and of
+//                  1/clip(A, 1e-3) (the M / M_depth / B scatter and the .sum(0)/B.sum(0) of
+//                  :169-191, summed in the reference's row order), plus
 //                  the per-frame L1 scales mean|T| (:197-198) and min/max for the loss history;
 //   snippet_grad — per snippet the analytic gradient of the L1 + inverse-depth L1 loss
 //                  (:200-203) w.r.t. its s and t (sign(A−T)/scale, the clip mask A ≥ 1e-3, the
 //                  −1/clip² of pow(−1)), reduced in f64 in a fixed order (deterministic);
 //   adam         — soft constraints λ2·mean(relu(1−s)²) + λ3·mean(t²) (:205-209) and
-//                  torch.optim.Adam's single-tensor update in its exact f32 op order (lerp,
-//                  mul+addcmul, sqrt/bc2_sqrt + eps, addcdiv), loss history row.
+//                  torch.optim.Adam's single-tensor update in its f32 op order (lerp — its weight < 0.5
+//                  branch as one fma —, mul+addcmul, sqrt/bc2_sqrt + eps, addcdiv), loss history row.
 // merge        — merge_scaled_triplets (:231-262): per frame the mean over all covering slots of
 //                s·x+t, rounded through the snippet dtype where the reference computes in it.
 // merge_moments — the same mean plus the per-pixel standard deviation of those slots' terms, in one pass
@@ -70,6 +71,15 @@ struct AlP {
   int ntot;
 };
 
+// __fmul_rn / __fadd_rn are header functions compiled outside this file's fp contract(off): where a mulrn
+// feeds an addrn directly the compiler contracts the pair to one fma, ONE rounding.  In the optimiser that is
+// A = x·s + t in frame_stats_body and snippet_grad_body (v_pk_fma_f32 / v_fma_f32; the reference and the oracle
+// round the product and the sum separately: A can differ from theirs by 1 ulp) and m + lw·diff in adam_param's
+// lw < 0.5 lerp branch (not taken at the default β1 = 0.5).  Every other mulrn / addrn pair has a division or a
+// second product between the two and stays two operations (v·β2 + (vw·g)·g is a packed multiply and an add), as
+// do the plain operators.  tests/aligner_util.py restates exactly this (fused=True) and
+// tests/test_aligner_step_gpu.py holds the kernels to it bitwise.  Writing the two as plain a * b, a + b under
+// the pragma gives the two roundings but measured 0.5 % slower per iteration (aligner) — not kept.
 __device__ __forceinline__ float mulrn(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float addrn(float a, float b) { return __fadd_rn(a, b); }
 
