@@ -4,7 +4,7 @@ Same constructor keywords, same `run(snippet_ls, dilations)` contract (plus `str
 reference's pipeline refuses above 1) and return value
 (merged [N,1,H,W] in the snippets' dtype, scales / translations as [n_d,1,1] f32, loss history
 as a list of (loss, min(summ), max(summ)) tuples).  The 2000-iteration Adam loop is enqueued
-entirely on the device (aligner.hip); the only host sync is reading the loss history at the end.
+entirely on the device (aligner.hip, merge.hip); the only host sync is reading the loss history at the end.
 """
 from __future__ import annotations
 
@@ -15,8 +15,8 @@ import torch
 from . import kernels as K
 
 
-MAX_DILATIONS = 8   # aligner.hip MAXD
-MAX_ROWS = 64       # aligner.hip MAXR: Σ snippet lengths (rows of the reference's M / M_depth / B tensors)
+MAX_DILATIONS = 8   # csrc/aligner_job.h MAXD
+MAX_ROWS = 64       # csrc/aligner_job.h MAXR: Σ snippet lengths (rows of the reference's M / M_depth / B tensors)
 
 
 def snippet_last(seq_len: int, length: int, dilation: int) -> int:

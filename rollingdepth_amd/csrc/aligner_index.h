@@ -3,7 +3,7 @@
 //   stride  frame step inside a snippet (the dilation)
 //   ss      start step: frame step between consecutive snippet starts (the reference's `stride`)
 //   last    N − win, win = (w − 1)·stride + 1: the start of the last window that fits N frames
-// One definition for the device code (aligner.hip), the host-side validation and the CPU check
+// One definition for the device code (aligner.hip, merge.hip), the host-side validation and the CPU check
 // programs (tests/cpp/aligner_index_check.cpp, cover_count_check.cpp): plain integer functions, no
 // other dependency.
 #pragma once

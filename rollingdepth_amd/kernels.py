@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -1049,43 +1050,79 @@ def aligner_optimize(xs: Sequence[torch.Tensor], scales: Sequence[torch.Tensor],
     return ws  # keep alive until the stream has consumed it
 
 
+def _int_array(values, at_least: int = 0):
+    values = [int(v) for v in values]
+    return (C.c_int * max(len(values), at_least))(*values)
+
+
+# The per-dilation arguments of a merge entry point as ctypes arrays (rdmi.h, rdmi_aligner_merge …).  They hold
+# raw pointers: the wrapper that holds the job keeps the tensors it was built from alive for the call.
+_MergeJob = namedtuple("_MergeJob", "nd x s t n stride k0 nloc w")
+
+
+def _merge_job(xf, scales, trans, strides, n=None, k0=None, w=None) -> _MergeJob:
+    """Whole snippets (n, k0, w None): xf[d] [n_d, w_d, …] holds every snippet of dilation d, so n and w come
+    from its shape and k0 is 0.  Rank-local: xf[d] holds the global snippets k0[d] … of the n[d] (None or 0
+    rows: the rank owns none, a null pointer travels), each w[d] long."""
+    nd = len(xf)
+    if n is None:
+        n, k0, w = [x.shape[0] for x in xf], [0] * nd, [x.shape[1] for x in xf]
+    return _MergeJob(nd, (C.c_void_p * nd)(*[(x.data_ptr() if x is not None and x.shape[0] else None) for x in xf]),
+                     (C.c_void_p * nd)(*[s.data_ptr() for s in scales]),
+                     (C.c_void_p * nd)(*[t.data_ptr() for t in trans]), _int_array(n), _int_array(strides),
+                     _int_array(k0), _int_array([(x.shape[0] if x is not None else 0) for x in xf]), _int_array(w))
+
+
+def _merge_mode(xf, f32_arith: bool) -> int:
+    """rdmi.h x_f32: 1 f32 snippets, 2 f16 snippets in f32 arithmetic, 0 f16 snippets in the reference's f16."""
+    return 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
+
+
+# What start_steps=None means to a wrapper.  _PLAIN_CALL: no array — the mean's wrappers then call the entry
+# point that takes no start steps and checks no layout, as before start steps existed.  _ALL_ONES: the entry
+# points since rdmi_version 6 always take start steps and always check the layout; None is all ones.
+_PLAIN_CALL, _ALL_ONES = "plain call", "all ones"
+
+
+def _start_step_array(what: str, start_steps, nd: int, none_means: str, seq_len: Optional[int] = 0):
+    """The start steps of a merge call as a C int array (seq_len: where a wrapper's own is optional)."""
+    if start_steps is None:
+        if none_means == _PLAIN_CALL:
+            return None
+        start_steps = [1] * nd
+    if len(start_steps) != nd:
+        raise ValueError(f"{what}: {len(start_steps)} start steps for {nd} dilations")
+    if seq_len is None:
+        raise ValueError(f"{what}: start_steps need seq_len (a snippet count does not determine it)")
+    return _int_array(start_steps)
+
+
+def _call_plain_or_strided(name: str, ssv, head, mid, tail=(), seq_len=None) -> None:
+    """lib.<name>(*head, *mid, *tail) when there are no start steps (ssv None); else lib.<name>_strided, which
+    takes the start steps after head (… n, stride) and, where the plain call has none, seq_len after mid (… w)."""
+    if ssv is not None:
+        name, head = name + "_strided", [*head, ssv]
+        mid = mid if seq_len is None else [*mid, int(seq_len)]
+    check(getattr(lib, name)(*head, *mid, *tail), name)
+
+
+def _piece_arrays(pieces: Sequence[Tuple[int, int]]):
+    """(count, first frames, frame counts) of a finish call's pieces; the arrays are never empty."""
+    return len(pieces), _int_array([p[0] for p in pieces], 1), _int_array([p[1] for p in pieces], 1)
+
+
 def aligner_merge(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: int, shift: torch.Tensor,
                   f32_arith: bool = False, start_steps: Optional[Sequence[int]] = None) -> torch.Tensor:
     """xf[d] [n_d, w_d, H, W] (f16/f32) → [seq_len, H, W] f32.  f16 snippets are merged in the
     reference's f16 arithmetic unless f32_arith (rdmi.h rdmi_aligner_merge x_f32 = 2).  start_steps:
     frames between snippet starts per dilation (rdmi_aligner_merge_strided; None: 1 everywhere)."""
-    nd = len(xf)
+    j = _merge_job(xf, scales, trans, strides)
     H, W = xf[0].shape[-2:]
-    wv = (C.c_int * nd)(*[x.shape[1] for x in xf])
+    ssv = _start_step_array("aligner_merge", start_steps, j.nd, _PLAIN_CALL)
     out = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
-    xp = (C.c_void_p * nd)(*[x.data_ptr() for x in xf])
-    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
-    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
-    nn = (C.c_int * nd)(*[x.shape[0] for x in xf])
-    stv = (C.c_int * nd)(*list(strides))
-    mode = 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
-    if start_steps is not None:
-        if len(start_steps) != nd:
-            raise ValueError(f"aligner_merge: {len(start_steps)} start steps for {nd} dilations")
-        ssv = (C.c_int * nd)(*[int(v) for v in start_steps])
-        check(lib.rdmi_aligner_merge_strided(nd, xp, mode, sp, tp, nn, stv, ssv, wv, seq_len, H * W,
-                                             shift.data_ptr(), out.data_ptr(), _stream()),
-              "rdmi_aligner_merge_strided")
-        return out
-    check(lib.rdmi_aligner_merge(nd, xp, mode, sp, tp, nn, stv, wv, seq_len, H * W,
-                                 shift.data_ptr(), out.data_ptr(), _stream()), "rdmi_aligner_merge")
+    _call_plain_or_strided("rdmi_aligner_merge", ssv, [j.nd, j.x, _merge_mode(xf, f32_arith), j.s, j.t, j.n, j.stride],
+                           [j.w, seq_len, H * W, shift.data_ptr(), out.data_ptr(), _stream()])
     return out
-
-
-def _start_step_array(what: str, start_steps: Optional[Sequence[int]], seq_len: Optional[int], nd: int):
-    """The start steps of a sharded-merge call as a C int array (None: the start-step-1 entry point)."""
-    if start_steps is None:
-        return None
-    if len(start_steps) != nd:
-        raise ValueError(f"{what}: {len(start_steps)} start steps for {nd} dilations")
-    if seq_len is None:
-        raise ValueError(f"{what}: start_steps need seq_len (a snippet count does not determine it)")
-    return (C.c_int * nd)(*[int(v) for v in start_steps])
 
 
 def aligner_merge_partial_window(xf: Sequence[Optional[torch.Tensor]], k0: Sequence[int], n: Sequence[int], scales,
@@ -1098,29 +1135,14 @@ def aligner_merge_partial_window(xf: Sequence[Optional[torch.Tensor]], k0: Seque
     s·x+t over frames f0 .. f0+nf-1 (a range the rank's snippets cover; `out`: a contiguous f64 [nf, HW]
     view to write into).  start_steps: frames between snippet starts per dilation, with the seq_len they
     are laid over (rdmi_aligner_merge_partial_window_strided; None: 1 everywhere)."""
-    nd = len(xf)
-    ssv = _start_step_array("aligner_merge_partial_window", start_steps, seq_len, nd)
+    ssv = _start_step_array("aligner_merge_partial_window", start_steps, len(xf), _PLAIN_CALL, seq_len)
     if out is None:
         out = torch.empty((nf, HW), dtype=torch.float64, device=shift.device)
     elif out.dtype != torch.float64 or tuple(out.shape) != (nf, HW) or not out.is_contiguous():
         raise ValueError("aligner_merge_partial_window: out must be contiguous f64 [nf, HW]")
-    xp = (C.c_void_p * nd)(*[(x.data_ptr() if x is not None and x.shape[0] else None) for x in xf])
-    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
-    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
-    nn = (C.c_int * nd)(*list(n))
-    kk = (C.c_int * nd)(*list(k0))
-    nl = (C.c_int * nd)(*[(x.shape[0] if x is not None else 0) for x in xf])
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*list(w))
-    if ssv is not None:
-        check(lib.rdmi_aligner_merge_partial_window_strided(nd, xp, int(x_f32), sp, tp, nn, stv, ssv, kk, nl, wv,
-                                                            int(seq_len), f0, nf, HW, shift.data_ptr(),
-                                                            out.data_ptr(), _stream()),
-              "rdmi_aligner_merge_partial_window_strided")
-        return out
-    check(lib.rdmi_aligner_merge_partial_window(nd, xp, int(x_f32), sp, tp, nn, stv, kk, nl, wv, f0, nf, HW,
-                                                shift.data_ptr(), out.data_ptr(), _stream()),
-          "rdmi_aligner_merge_partial_window")
+    j = _merge_job(xf, scales, trans, strides, n, k0, w)
+    _call_plain_or_strided("rdmi_aligner_merge_partial_window", ssv, [j.nd, j.x, int(x_f32), j.s, j.t, j.n, j.stride],
+                           [j.k0, j.nloc, j.w], [f0, nf, HW, shift.data_ptr(), out.data_ptr(), _stream()], seq_len)
     return out
 
 
@@ -1134,36 +1156,16 @@ def aligner_merge_finish_pieces(recv: torch.Tensor, pieces: Sequence[Tuple[int, 
     cover count of the strided layout, 0 — and a 0 output — at a frame no snippet reaches)."""
     if recv.dtype != torch.float64:
         raise TypeError("aligner_merge_finish_pieces: f64 sums expected")
-    nd, npc = len(n), len(pieces)
-    ssv = _start_step_array("aligner_merge_finish_pieces", start_steps, seq_len, nd)
+    ssv = _start_step_array("aligner_merge_finish_pieces", start_steps, len(n), _PLAIN_CALL, seq_len)
     if out is None:
         out = torch.empty((nf, HW), dtype=F32, device=recv.device)
     elif out.dtype != F32 or tuple(out.shape) != (nf, HW) or not out.is_contiguous():
         raise ValueError("aligner_merge_finish_pieces: out must be contiguous f32 [nf, HW]")
-    nn = (C.c_int * nd)(*list(n))
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*list(w))
-    pf = (C.c_int * max(npc, 1))(*[p[0] for p in pieces])
-    pn = (C.c_int * max(npc, 1))(*[p[1] for p in pieces])
-    if ssv is not None:
-        check(lib.rdmi_aligner_merge_finish_pieces_strided(nd, nn, stv, ssv, wv, int(seq_len), f0, nf, HW, npc, pf, pn,
-                                                           recv.data_ptr() if recv.numel() else None,
-                                                           out.data_ptr(), _stream()),
-              "rdmi_aligner_merge_finish_pieces_strided")
-        return out
-    check(lib.rdmi_aligner_merge_finish_pieces(nd, nn, stv, wv, f0, nf, HW, npc, pf, pn,
-                                               recv.data_ptr() if recv.numel() else None, out.data_ptr(),
-                                               _stream()), "rdmi_aligner_merge_finish_pieces")
+    _call_plain_or_strided("rdmi_aligner_merge_finish_pieces", ssv, [len(n), _int_array(n), _int_array(strides)],
+                           [_int_array(w)], [f0, nf, HW, *_piece_arrays(pieces),
+                                             recv.data_ptr() if recv.numel() else None, out.data_ptr(), _stream()],
+                           seq_len)
     return out
-
-
-def _ones_or(what: str, start_steps: Optional[Sequence[int]], nd: int):
-    """The start steps of a moments call (they always travel; None: all ones) as a C int array."""
-    if start_steps is None:
-        start_steps = [1] * nd
-    if len(start_steps) != nd:
-        raise ValueError(f"{what}: {len(start_steps)} start steps for {nd} dilations")
-    return (C.c_int * nd)(*[int(v) for v in start_steps])
 
 
 def aligner_merge_moments(xf: Sequence[torch.Tensor], scales, trans, strides, seq_len: int, shift: torch.Tensor,
@@ -1173,20 +1175,14 @@ def aligner_merge_moments(xf: Sequence[torch.Tensor], scales, trans, strides, se
     [n_d, w_d, H, W] (f16/f32) → (mean, std), both [seq_len, H, W] f32.  The mean is aligner_merge's,
     bitwise; std is the population standard deviation of the frame's covering terms s·(x − shift) + t in
     the units of the mean, 0 where fewer than two terms cover a pixel.  start_steps: as aligner_merge."""
-    nd = len(xf)
     H, W = xf[0].shape[-2:]
-    ssv = _ones_or("aligner_merge_moments", start_steps, nd)
+    ssv = _start_step_array("aligner_merge_moments", start_steps, len(xf), _ALL_ONES)
     mean = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
     std = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
-    xp = (C.c_void_p * nd)(*[x.data_ptr() for x in xf])
-    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
-    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
-    nn = (C.c_int * nd)(*[x.shape[0] for x in xf])
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*[x.shape[1] for x in xf])
-    mode = 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
-    check(lib.rdmi_aligner_merge_moments(nd, xp, mode, sp, tp, nn, stv, ssv, wv, seq_len, H * W, shift.data_ptr(),
-                                         mean.data_ptr(), std.data_ptr(), _stream()), "rdmi_aligner_merge_moments")
+    j = _merge_job(xf, scales, trans, strides)
+    check(lib.rdmi_aligner_merge_moments(j.nd, j.x, _merge_mode(xf, f32_arith), j.s, j.t, j.n, j.stride, ssv, j.w,
+                                         seq_len, H * W, shift.data_ptr(), mean.data_ptr(), std.data_ptr(),
+                                         _stream()), "rdmi_aligner_merge_moments")
     return mean, std
 
 
@@ -1198,23 +1194,16 @@ def aligner_merge_partial_window_moments(xf: Sequence[Optional[torch.Tensor]], k
     """aligner_merge_partial_window for both moments (rdmi_aligner_merge_partial_window_moments): → f64
     [nf, 2, HW], per frame the sum of the rank's covering terms s·(x − shift) + t, then the sum of their
     squares.  seq_len is always needed (the layout is always checked); start_steps None: all ones."""
-    nd = len(xf)
-    ssv = _ones_or("aligner_merge_partial_window_moments", start_steps, nd)
+    ssv = _start_step_array("aligner_merge_partial_window_moments", start_steps, len(xf), _ALL_ONES)
     if out is None:
         out = torch.empty((nf, 2, HW), dtype=torch.float64, device=shift.device)
     elif out.dtype != torch.float64 or tuple(out.shape) != (nf, 2, HW) or not out.is_contiguous():
         raise ValueError("aligner_merge_partial_window_moments: out must be contiguous f64 [nf, 2, HW]")
-    xp = (C.c_void_p * nd)(*[(x.data_ptr() if x is not None and x.shape[0] else None) for x in xf])
-    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
-    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
-    nn = (C.c_int * nd)(*list(n))
-    kk = (C.c_int * nd)(*list(k0))
-    nl = (C.c_int * nd)(*[(x.shape[0] if x is not None else 0) for x in xf])
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*list(w))
-    check(lib.rdmi_aligner_merge_partial_window_moments(nd, xp, int(x_f32), sp, tp, nn, stv, ssv, kk, nl, wv,
-                                                        int(seq_len), f0, nf, HW, shift.data_ptr(), out.data_ptr(),
-                                                        _stream()), "rdmi_aligner_merge_partial_window_moments")
+    j = _merge_job(xf, scales, trans, strides, n, k0, w)
+    check(lib.rdmi_aligner_merge_partial_window_moments(j.nd, j.x, int(x_f32), j.s, j.t, j.n, j.stride, ssv, j.k0,
+                                                        j.nloc, j.w, int(seq_len), f0, nf, HW, shift.data_ptr(),
+                                                        out.data_ptr(), _stream()),
+          "rdmi_aligner_merge_partial_window_moments")
     return out
 
 
@@ -1226,16 +1215,11 @@ def aligner_merge_finish_pieces_moments(recv: torch.Tensor, pieces: Sequence[Tup
     [Σ nf_q, 2, HW] → (mean, std), both f32 [nf, HW]."""
     if recv.dtype != torch.float64:
         raise TypeError("aligner_merge_finish_pieces_moments: f64 sums expected")
-    nd, npc = len(n), len(pieces)
-    ssv = _ones_or("aligner_merge_finish_pieces_moments", start_steps, nd)
+    ssv = _start_step_array("aligner_merge_finish_pieces_moments", start_steps, len(n), _ALL_ONES)
     mean = torch.empty((nf, HW), dtype=F32, device=recv.device)
     std = torch.empty((nf, HW), dtype=F32, device=recv.device)
-    nn = (C.c_int * nd)(*list(n))
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*list(w))
-    pf = (C.c_int * max(npc, 1))(*[p[0] for p in pieces])
-    pn = (C.c_int * max(npc, 1))(*[p[1] for p in pieces])
-    check(lib.rdmi_aligner_merge_finish_pieces_moments(nd, nn, stv, ssv, wv, int(seq_len), f0, nf, HW, npc, pf, pn,
+    check(lib.rdmi_aligner_merge_finish_pieces_moments(len(n), _int_array(n), _int_array(strides), ssv, _int_array(w),
+                                                       int(seq_len), f0, nf, HW, *_piece_arrays(pieces),
                                                        recv.data_ptr() if recv.numel() else None,
                                                        mean.data_ptr() if nf else None,
                                                        std.data_ptr() if nf else None, _stream()),
@@ -1252,21 +1236,14 @@ def aligner_merge_median(xf: Sequence[torch.Tensor], scales, trans, strides, seq
     mean of the two middle ones.  start_steps: as aligner_merge."""
     if not isinstance(mad, bool):
         raise TypeError(f"aligner_merge_median: mad must be a bool, got {type(mad).__name__}")
-    nd = len(xf)
     H, W = xf[0].shape[-2:]
-    ssv = _ones_or("aligner_merge_median", start_steps, nd)
+    ssv = _start_step_array("aligner_merge_median", start_steps, len(xf), _ALL_ONES)
     med = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device)
     dev = torch.empty((seq_len, H, W), dtype=F32, device=xf[0].device) if mad else None
-    xp = (C.c_void_p * nd)(*[x.data_ptr() for x in xf])
-    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
-    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
-    nn = (C.c_int * nd)(*[x.shape[0] for x in xf])
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*[x.shape[1] for x in xf])
-    mode = 1 if xf[0].dtype == F32 else (2 if f32_arith else 0)
-    check(lib.rdmi_aligner_merge_median(nd, xp, mode, sp, tp, nn, stv, ssv, wv, seq_len, H * W, shift.data_ptr(),
-                                        med.data_ptr(), dev.data_ptr() if mad else None, _stream()),
-          "rdmi_aligner_merge_median")
+    j = _merge_job(xf, scales, trans, strides)
+    check(lib.rdmi_aligner_merge_median(j.nd, j.x, _merge_mode(xf, f32_arith), j.s, j.t, j.n, j.stride, ssv, j.w,
+                                        seq_len, H * W, shift.data_ptr(), med.data_ptr(),
+                                        dev.data_ptr() if mad else None, _stream()), "rdmi_aligner_merge_median")
     return (med, dev) if mad else med
 
 
@@ -1279,27 +1256,20 @@ def aligner_merge_partial_window_terms(xf: Sequence[Optional[torch.Tensor]], k0:
     (rdmi_aligner_merge_partial_window_terms): frame f0 + i's go to rows row_off[i] … row_off[i + 1] − 1 of
     out (f32 [rows, HW], contiguous) in the merge's order.  row_off: int32 [nf + 1] on the device; the
     library recounts out's rows from the index map and refuses another count."""
-    nd = len(xf)
     what = "aligner_merge_partial_window_terms"
-    ssv = _ones_or(what, start_steps, nd)
+    ssv = _start_step_array(what, start_steps, len(xf), _ALL_ONES)
     if out.dtype != F32 or out.dim() != 2 or out.shape[1] != HW or not out.is_contiguous():
         raise ValueError(f"{what}: out must be contiguous f32 [rows, HW]")
     if row_off.dtype != torch.int32 or tuple(row_off.shape) != (nf + 1,) or not row_off.is_contiguous():
         raise ValueError(f"{what}: row_off must be contiguous int32 [nf + 1]")
     if row_off.device != out.device:
         raise ValueError(f"{what}: row_off on {row_off.device}, out on {out.device}")
-    xp = (C.c_void_p * nd)(*[(x.data_ptr() if x is not None and x.shape[0] else None) for x in xf])
-    sp = (C.c_void_p * nd)(*[s.data_ptr() for s in scales])
-    tp = (C.c_void_p * nd)(*[t.data_ptr() for t in trans])
-    nn = (C.c_int * nd)(*list(n))
-    kk = (C.c_int * nd)(*list(k0))
-    nl = (C.c_int * nd)(*[(x.shape[0] if x is not None else 0) for x in xf])
-    stv = (C.c_int * nd)(*list(strides))
-    wv = (C.c_int * nd)(*list(w))
-    check(lib.rdmi_aligner_merge_partial_window_terms(nd, xp, int(x_f32), sp, tp, nn, stv, ssv, kk, nl, wv,
-                                                      int(seq_len), f0, nf, HW, shift.data_ptr(), row_off.data_ptr(),
-                                                      out.shape[0], out.data_ptr() if out.numel() else None,
-                                                      _stream()), "rdmi_aligner_merge_partial_window_terms")
+    j = _merge_job(xf, scales, trans, strides, n, k0, w)
+    check(lib.rdmi_aligner_merge_partial_window_terms(j.nd, j.x, int(x_f32), j.s, j.t, j.n, j.stride, ssv, j.k0,
+                                                      j.nloc, j.w, int(seq_len), f0, nf, HW, shift.data_ptr(),
+                                                      row_off.data_ptr(), out.shape[0],
+                                                      out.data_ptr() if out.numel() else None, _stream()),
+          "rdmi_aligner_merge_partial_window_terms")
     return out
 
 

@@ -32,7 +32,7 @@ Outputs stay distributed: rank r holds depth / coaligned depth for frames chunk_
 
 Numerics vs the single-GPU forward: identical per-snippet arithmetic.  The cross-rank sums — the
 merge of s·x+t per frame and refine's per-frame average of snippet predictions — are f64 sums on
-both paths (aligner.hip merge_k, elementwise.hip snippet_*): exact for f16 terms, and for f32 terms
+both paths (merge.hip merge_k, elementwise.hip snippet_*): exact for f16 terms, and for f32 terms
 exact unless a frame's terms span more than ≈29 exponent bits (rare), so the order RCCL reduces them
 in does not change a bit in practice; the aligner runs the same kernel on the same (all-gathered)
 inputs.  What can still differ is the kernel engine chosen per launch shape (the f32 accumulation

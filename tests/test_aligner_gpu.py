@@ -1,4 +1,4 @@
-"""DepthAligner kernels (aligner.hip) vs the numpy oracle (oracle/rd_oracle.py), which is itself
+"""DepthAligner kernels (aligner.hip, merge.hip) vs the numpy oracle (oracle/rd_oracle.py), which is itself
 pinned to the reference's DepthAligner.run in tests/test_oracle_golden.py."""
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """Snippet strides > 1 on the device: the co-alignment kernels and the merge with snippets that start
-every `stride` frames plus the last window (aligner.hip, csrc/aligner_index.h) against the numpy
+every `stride` frames plus the last window (aligner.hip, merge.hip, csrc/aligner_index.h) against the numpy
 oracle with the same strided index arrays (itself pinned to a strided run of the reference's
 DepthAligner in tests/test_strided_cpu.py), and RollingDepthPipeline.forward with strides."""
 import functools

@@ -1,5 +1,5 @@
 """Bit fingerprints of DepthAligner.run (scales, translations, loss history, merged depth) for A/B builds
-that must be bitwise equal (schedule-only changes to aligner.hip): run once per library and diff.
+that must be bitwise equal (schedule-only changes to aligner.hip or merge.hip): run once per library and diff.
 
     python tools/aligner_bits.py > a.txt; RDMI_LIB=tools/librdmi_ab_old.so python tools/aligner_bits.py > b.txt
     diff a.txt b.txt
