@@ -719,6 +719,53 @@ int rdmi_flow_estimate(const void* frames, int dtype, long stride_n, long stride
                        int backward, float alpha, float beta, float* flow, float* flow_bwd, unsigned char* valid,
                        void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Guided upsampling (since rdmi_version 11): joint bilateral upsampling (Kopf et al. 2007) of low-resolution maps
+ * along a full-resolution guide image — the edge-aware alternative to rdmi_resize for restore_res: a depth
+ * discontinuity lands where the image edge is instead of becoming a ramp.  Deterministic, no learned part; the
+ * reference has no counterpart.
+ *
+ * values [N][C][h][w] contiguous, RDMI_F16 (widened exactly) or RDMI_F32, C = 1 … 4 channels that share one set of
+ *   weights.  guide_lo [N][3][h][w] f32 contiguous: the guide at the values' resolution.  guide_hi: element
+ *   (n, c, Y, X) at guide_hi + n·sn + c·sc + Y·sy + X·sx (elements; rdmi_resize's addressing, so rgb24 frames
+ *   [N][H][W][3] and planar f32 are the same call) of dtype RDMI_U8 or RDMI_F32; G = (float)element · guide_scale,
+ *   one rounding (1/255 for u8 frames against a guide_lo in [0, 1]).  out [N][C][H][W] f32 contiguous.
+ * Output pixel (Y, X) of frame n.  All arithmetic is f32; every operation below is rounded once, and only where an
+ *   fma is written are a product and a sum contracted.
+ *     yl = ((float)Y + 0.5)·(h / H) − 0.5 with h / H the f32 quotient of the two sizes converted to f32, product and
+ *       difference rounded separately; xl alike with w / W.  y0 = ⌊yl⌋, x0 = ⌊xl⌋.
+ *     Taps q = (qy, qx), qy = y0 − r + 1 … y0 + r (outer), qx = x0 − r + 1 … x0 + r (inner), both ascending: (2r)² taps
+ *       in row-major order.  A tap outside the h × w image is skipped; at least one always lies inside.
+ *     cs = log₂e / (2·σs²) and cr = log₂e / (2·σr²), each formed in f64 and rounded to f32 once (the exponent is
+ *       kept in base 2: the weight below is 2^−(e − m), which is exp(−(e − m)) of the natural-base exponent).
+ *     e_q = min(fma(D, cr, (qy − yl)²·cs + (qx − xl)²·cs), FLT_MAX), D = fma(d₂, d₂, fma(d₁, d₁, d₀·d₀)),
+ *       d_c = G[n, c, Y, X] − guide_lo[n, c, q]; (qy − yl)²·cs is ((qy − yl)·(qy − yl))·cs.  The min, which returns
+ *       FLT_MAX for a NaN, only matters for a σ so small that cs or cr overflows: the exponents stay finite.
+ *     m = min_q e_q over the taps inside the image; w_q = exp2(m − e_q), the hardware v_exp_f32 (1 ulp).
+ *     out[n, k, Y, X] = Σ_q w_q·v[n, k, q] / Σ_q w_q, evaluated as v_b + (Σ_q w_q·(v_q − v_b)) / (Σ_q w_q) with v_b the
+ *       value at the base tap (min(max(y0, 0), h − 1), min(max(x0, 0), w − 1)), which is always one of the taps: both
+ *       sums start at +0 and run over the taps in the order above, the numerator as acc = fma(w_q, v_q − v_b, acc);
+ *       the quotient is the IEEE division.  So a constant plane comes out exactly, and the rounding errors scale
+ *       with the range of the values over the taps, not with |v|.
+ *   The largest weight is exactly 1, so Σw ≥ 1 and no σ gives 0/0.  Inputs are finite: NaN is not part of the
+ *   contract.
+ * One launch: a workgroup owns a 16 × 64 tile of output pixels of one frame and stages the tile's low-resolution
+ *   footprint (at most (16 + 2r + 1) × (64 + 2r + 1) pixels since h ≤ H and w ≤ W) in LDS.  No atomics, no workspace,
+ *   no allocation, nothing synchronises: graph-capturable like every other entry point.  A pixel's arithmetic is that
+ *   of one lane in the fixed order above and reads that frame's inputs only, element by element (there is no
+ *   wide-load path): the bits do not depend on N, on the other frames, on C (a channel computed alone equals the same
+ *   channel computed among four), on the pointers' alignment, or on the call.
+ * RDMI_E_ARG before any launch: a null values / guide_lo / guide_hi / out, N, h, w, H or W < 1, C outside 1 … 4,
+ *   radius outside 1 … RDMI_JBU_MAX_RADIUS, a σ that is ≤ 0 or NaN, a values dtype other than RDMI_F16 / RDMI_F32, a
+ *   guide dtype other than RDMI_U8 / RDMI_F32.
+ * RDMI_E_UNSUPPORTED (rdmi_last_error says which): H < h or W < w — an upsampler; equal sizes are allowed and make it
+ *   a joint bilateral filter — or more than 2^31 − 1 tiles in all N frames. */
+#define RDMI_JBU_MAX_RADIUS 3
+int rdmi_joint_bilateral_upsample(const void* values, int values_dtype, const float* guide_lo, const void* guide_hi,
+                                  int guide_dtype, long sn, long sc, long sy, long sx, float guide_scale, int N, int C,
+                                  int h, int w, int H, int W, int radius, float sigma_spatial, float sigma_range,
+                                  float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ Public surface mirrors the reference: RollingDepthPipeline / RollingDepthOutput
 modified diffusers attention processor (CrossFrameAttnProcessor); depth_metrics / align_scale_shift
 (metrics.py) score a depth video after a least-squares scale and shift, temporal_metrics its change
 from frame to frame, optical_flow (flow.py) estimates the flow and occlusion mask that score needs from the
-RGB frames; quantiles (kernels.py) takes exact order statistics of a device tensor.  All arithmetic runs in
+RGB frames; quantiles (kernels.py) takes exact order statistics of a device tensor; guided_upsample (upsample.py)
+brings a depth video to the frames' resolution with its edges on the image's.  All arithmetic runs in
 librdmi.so (HIP); importing the compute modules without the built library raises.
 """
 __version__ = "0.1.0"
@@ -27,6 +28,9 @@ def __getattr__(name):
     if name in ("optical_flow", "OpticalFlow"):
         from . import flow
         return getattr(flow, name)
+    if name == "guided_upsample":
+        from .upsample import guided_upsample
+        return guided_upsample
     if name == "quantiles":
         from .kernels import quantiles
         return quantiles

@@ -161,6 +161,8 @@ _SIGS = {
     "rdmi_flow_fb_check": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp]),
     "rdmi_flow_estimate": (i32, [vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, f32, i32, f32, f32,
                                  vp, vp, vp, vp, vp]),
+    "rdmi_joint_bilateral_upsample": (i32, [vp, i32, vp, vp, i32, i64, i64, i64, i64, f32, i32, i32, i32, i32, i32,
+                                            i32, i32, f32, f32, vp, vp]),
 }
 
 RDMI_F16, RDMI_F32, RDMI_U8, RDMI_F32_X3, RDMI_F32_X6 = 0, 1, 2, 3, 4

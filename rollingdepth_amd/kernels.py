@@ -1706,3 +1706,58 @@ def flow_estimate(frames: torch.Tensor, frame_step: int = 1, levels: Optional[in
                                      iterations, damping, int(backward), alpha, beta, flow.data_ptr(), _p(bwd),
                                      _p(valid), ws.data_ptr(), _stream()), "rdmi_flow_estimate")
     return flow, bwd, valid
+
+
+# ----------------------------------------------------------------------------- guided upsampling
+JBU_MAX_RADIUS = 3  # RDMI_JBU_MAX_RADIUS
+JBU_MAX_CHANNELS = 4
+
+
+def joint_bilateral_upsample(values: torch.Tensor, guide_lo: torch.Tensor, guide_hi: torch.Tensor, radius: int = 2,
+                             sigma_spatial: float = 1.0, sigma_range: float = 0.1,
+                             channels_last: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rdmi_joint_bilateral_upsample: values [N, C, h, w] (f16 / f32, C ≤ 4, contiguous) → f32 [N, C, H, W] along the
+    guide.  guide_lo: f32 [N, 3, h, w] contiguous.  guide_hi: uint8 or f32, [N, 3, H, W] (any strides), or
+    [N, H, W, 3] with channels_last=True; None takes uint8 as decoded rgb24 frames (channels last) and f32 as planar.
+    The guide's dtype sets guide_scale: 1/255 for uint8, 1 for f32."""
+    _need_act(values, "joint_bilateral_upsample.values")
+    _need(guide_lo, F32, "joint_bilateral_upsample.guide_lo")
+    if not guide_hi.is_cuda:
+        raise ValueError(f"joint_bilateral_upsample.guide_hi: expected a device tensor, got {guide_hi.device}")
+    if guide_hi.dtype == torch.uint8:
+        code, guide_scale = _N.RDMI_U8, 1.0 / 255.0
+    elif guide_hi.dtype == F32:
+        code, guide_scale = _N.RDMI_F32, 1.0
+    else:
+        raise TypeError(f"joint_bilateral_upsample.guide_hi: uint8 or float32 expected, got {guide_hi.dtype}")
+    if values.dim() != 4 or guide_lo.dim() != 4 or guide_hi.dim() != 4:
+        raise ValueError(f"joint_bilateral_upsample: 4-D tensors expected, got {tuple(values.shape)}, "
+                         f"{tuple(guide_lo.shape)} and {tuple(guide_hi.shape)}")
+    if channels_last is None:
+        channels_last = guide_hi.dtype == torch.uint8
+    if channels_last:
+        Ng, H, W, Cg = guide_hi.shape
+        sn, sy, sx, sc = guide_hi.stride()
+    else:
+        Ng, Cg, H, W = guide_hi.shape
+        sn, sc, sy, sx = guide_hi.stride()
+    N, Cc, h, w = values.shape
+    if not 1 <= Cc <= JBU_MAX_CHANNELS:
+        raise ValueError(f"joint_bilateral_upsample.values: 1 … {JBU_MAX_CHANNELS} channels, got {tuple(values.shape)}")
+    if Cg != 3 or Ng != N:
+        raise ValueError(f"joint_bilateral_upsample.guide_hi: {N} frames of three channels expected, got "
+                         f"{tuple(guide_hi.shape)}")
+    if guide_lo.shape != (N, 3, h, w):
+        raise ValueError(f"joint_bilateral_upsample.guide_lo: {(N, 3, h, w)} expected, got {tuple(guide_lo.shape)}")
+    if not (values.is_contiguous() and guide_lo.is_contiguous()):
+        raise ValueError("joint_bilateral_upsample: values and guide_lo must be contiguous")
+    if out is None:
+        out = torch.empty((N, Cc, H, W), dtype=F32, device=values.device)
+    if out.shape != (N, Cc, H, W) or out.dtype != F32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("joint_bilateral_upsample: out must be a contiguous f32 [N, C, H, W] device tensor")
+    with _Timed("joint_bilateral_upsample", 0, shape=(N, Cc, h, w, H, W, radius)):
+        check(lib.rdmi_joint_bilateral_upsample(values.data_ptr(), _dtype_code(values), guide_lo.data_ptr(),
+                                                guide_hi.data_ptr(), code, sn, sc, sy, sx, guide_scale, N, Cc, h, w,
+                                                H, W, int(radius), float(sigma_spatial), float(sigma_range),
+                                                out.data_ptr(), _stream()), "rdmi_joint_bilateral_upsample")
+    return out

@@ -205,6 +205,25 @@ def check_renorm_percentiles(renorm_percentiles) -> Optional[Tuple[float, float]
     return float(p[0]), float(p[1])
 
 
+RESTORE_METHODS = ("resize", "joint_bilateral")
+_RESTORE_KWARGS = ("radius", "sigma_spatial", "sigma_range")
+
+
+def check_restore_method(restore_method, restore_kwargs=None) -> Tuple[str, Dict]:
+    """`restore_method` must be "resize" or "joint_bilateral" and `restore_kwargs` None or a dict with keys among
+    radius, sigma_spatial and sigma_range (ValueError otherwise, before any device work; the values are checked
+    by upsample.check_upsample_args once the frames are known).  Returns the method and the keywords as a dict."""
+    if not isinstance(restore_method, str) or restore_method not in RESTORE_METHODS:
+        raise ValueError(f'restore_method must be "resize" or "joint_bilateral", got {restore_method!r}')
+    kw = {} if restore_kwargs is None else restore_kwargs
+    if not isinstance(kw, dict) or any(k not in _RESTORE_KWARGS for k in kw):
+        raise ValueError(f"restore_kwargs must be None or a dict with keys among {_RESTORE_KWARGS}, got "
+                         f"{restore_kwargs!r}")
+    if kw and restore_method != "joint_bilateral":
+        raise ValueError('restore_kwargs belong to restore_method="joint_bilateral"')
+    return restore_method, dict(kw)
+
+
 class RollingDepthPipeline:
     rgb_latent_scale_factor = 0.18215
     depth_latent_scale_factor = 0.18215
@@ -601,7 +620,8 @@ class RollingDepthPipeline:
                  verbose: bool = False, max_vae_bs: int = 4, unload_snippet: bool = False,
                  restore_res: bool = False, input_fg_video_path=None, refine_stride: int = 1,
                  output_uncertainty: bool = False, merge: str = "mean",
-                 renorm_percentiles: Optional[Tuple[float, float]] = None, **kw) -> RollingDepthOutput:
+                 renorm_percentiles: Optional[Tuple[float, float]] = None, restore_method: str = "resize",
+                 restore_kwargs: Optional[Dict] = None, **kw) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:78-176.  `input_video_path` (or the fork's `input_fg_video_path`):
         a video file (decoding needs PyAV, absent from this image), decoded uint8 rgb24 frames
         [N, H, W, 3] (numpy / torch: resized to processing_res and normalised on the device,
@@ -609,22 +629,35 @@ class RollingDepthPipeline:
         (used as is: processing_res and restore_res do not apply to it).  `refine_stride` (the build's own,
         1 … refine_snippet_len), `output_uncertainty`, `merge` ("mean" | "median") and `renorm_percentiles`
         (None | (lo, hi)): see forward().
-        restore_res resizes depth_uncertainty as it resizes depth_pred."""
+        restore_res resizes depth_uncertainty as it resizes depth_pred.
+        `restore_method` (the build's own, "resize" | "joint_bilateral"; anything else is a ValueError): how
+        restore_res brings depth_pred (and depth_uncertainty) back to the video's resolution.  "resize" is the
+        reference's antialiased resize.  "joint_bilateral" upsamples both maps in one call along the original
+        frames (upsample.guided_upsample; `restore_kwargs`: its radius, sigma_spatial, sigma_range), so that depth
+        edges land on image edges instead of becoming ramps; input_rgb is resized as before.  It needs restore_res
+        and a video no smaller than the processing resolution in either dimension (ValueError before any
+        inference), and it keeps the decoded uint8 frames on the device from ingest to restore: 500 frames of
+        1080p are 3.1 GB, beside what the large-resolution warning below is about."""
         check_refine_stride(refine_stride, refine_snippet_len)
         check_output_uncertainty(output_uncertainty)
         check_merge(merge)
         check_renorm_percentiles(renorm_percentiles)
+        restore_method, restore_kwargs = check_restore_method(restore_method, restore_kwargs)
+        guided = restore_method == "joint_bilateral"
+        if guided and not restore_res:
+            raise ValueError('restore_method="joint_bilateral" needs restore_res=True')
         assert processing_res >= 0
         if processing_res > 1024:
             logging.warning(f"Procssing at high-resolution ({processing_res}) may lead to suboptimal accuracy.")
         src = input_fg_video_path if input_fg_video_path is not None else input_video_path
-        original_res = None
+        original_res = source = None
         if isinstance(src, torch.Tensor) and src.is_floating_point():
             frames = src
         else:
             from .video_io import load_video_frames
-            frames, original_res = load_video_frames(src, start_frame, frame_count, processing_res, resample_method,
-                                                     verbose, device=self.device)
+            frames, original_res, *source = load_video_frames(src, start_frame, frame_count, processing_res,
+                                                              resample_method, verbose, device=self.device,
+                                                              **(dict(return_source=True) if guided else {}))
         if restore_res:
             if original_res is None:
                 raise ValueError("restore_res needs the original resolution: pass the video or its decoded uint8 "
@@ -632,6 +665,14 @@ class RollingDepthPipeline:
             if max(original_res) > 2048:
                 logging.warning(f"Resizing back to large resolution ({list(original_res)}) may result in significant "
                                 "memory usage.")
+            if guided:
+                from .upsample import check_upsample_args
+                if original_res[0] < frames.shape[-2] or original_res[1] < frames.shape[-1]:
+                    raise ValueError(f'restore_method="joint_bilateral" only upsamples: the video is {original_res[0]} x '
+                                     f"{original_res[1]}, below the processing resolution {frames.shape[-2]} x "
+                                     f"{frames.shape[-1]}")
+                check_upsample_args(torch.empty((frames.shape[0], 1) + tuple(frames.shape[-2:]), device="meta"),
+                                    source[0], **restore_kwargs)
         kw.pop("input_bg_video_path", None)  # fork CLI (run_video.py:563): IC-Light background, unused here
         out = self.forward(frames[None] if frames.dim() == 4 else frames, dilations, cap_dilation, snippet_lengths,
                            init_infer_steps, strides, coalign_kwargs, refine_step, refine_snippet_len,
@@ -641,10 +682,19 @@ class RollingDepthPipeline:
                            **(dict(renorm_percentiles=renorm_percentiles) if renorm_percentiles is not None else {}),
                            **kw)
         if restore_res:  # rollingdepth_pipeline.py:155-173 (torchvision resize, antialias=True), on the device
-            for name in ("input_rgb", "depth_pred") + (("depth_uncertainty",) if output_uncertainty else ()):
+            maps = ("depth_pred",) + (("depth_uncertainty",) if output_uncertainty else ())
+            for name in ("input_rgb",) + (() if guided else maps):
                 t = getattr(out, name)
                 r = K.resize(t.to(self.device, torch.float32), original_res, resample_method.upper())
                 setattr(out, name, r.to(t.dtype).cpu())
+            if guided:  # both maps through one launch per chunk of frames: they share the weights
+                from .upsample import upsample_on_device
+                ts = [getattr(out, name) for name in maps]
+                lo = torch.cat([t.to(self.device, torch.float32) for t in ts], dim=1)
+                r = upsample_on_device(lo, source[0], out_dtype=torch.float32,
+                                       **dict(dict(radius=2, sigma_spatial=1.0, sigma_range=0.1), **restore_kwargs))
+                for k, (name, t) in enumerate(zip(maps, ts)):
+                    setattr(out, name, r[:, k:k + 1].to(t.dtype).cpu().contiguous())
         if input_fg_video_path is not None:
             rgb = out.depth_pred.float() * 0.5 + 0.5
             out.R_pred = out.G_pred = out.B_pred = rgb

@@ -34,9 +34,11 @@ def resize_max_res(img: torch.Tensor, max_edge_resolution: int, resample_method:
 
 
 def frames_from_rgb24(frames: Union[np.ndarray, torch.Tensor], processing_res: int = 0,
-                      resample_method: str = "BILINEAR", device="cuda") -> Tuple[torch.Tensor, Tuple[int, int]]:
+                      resample_method: str = "BILINEAR", device="cuda", return_source: bool = False):
     """Decoded uint8 [N, H, W, 3] frames → (f32 [N, 3, h, w] in [-1, 1] on the device, (H, W)):
-    video_io.py:104-123 for every frame at once."""
+    video_io.py:104-123 for every frame at once.  return_source=True appends the uploaded uint8 frames (on the
+    device, [N, H, W, 3]) as a third value instead of dropping them: the guide of an edge-aware restore_res
+    (upsample.py).  They stay allocated as long as the caller holds them: 500 frames of 1080p are 3.1 GB."""
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
@@ -47,13 +49,15 @@ def frames_from_rgb24(frames: Union[np.ndarray, torch.Tensor], processing_res: i
     dev = frames.to(device, non_blocking=True)
     h, w = _target_size(h0, w0, processing_res) if processing_res > 0 else (h0, w0)
     out = K.resize(dev, (h, w), str(resample_method).upper().split(".")[-1], normalize=True, channels_last=True)
-    return out, (h0, w0)
+    return (out, (h0, w0), dev) if return_source else (out, (h0, w0))
 
 
 def load_video_frames(input_path, start_frame: int = 0, frame_count: int = 0, processing_res: int = 0,
-                      resample_method: str = "BILINEAR", verbose: bool = False, device="cuda"):
+                      resample_method: str = "BILINEAR", verbose: bool = False, device="cuda",
+                      return_source: bool = False):
     """video_io.py:71-137.  `input_path`: a video file (needs PyAV) or already-decoded uint8 rgb24
-    frames [N, H, W, 3] (numpy / torch).  Returns (f32 [N, 3, h, w] in [-1, 1] on `device`, (H, W))."""
+    frames [N, H, W, 3] (numpy / torch).  Returns (f32 [N, 3, h, w] in [-1, 1] on `device`, (H, W)), and with
+    return_source=True the uint8 frames on `device` as a third value (frames_from_rgb24)."""
     assert start_frame >= 0
     if isinstance(input_path, (np.ndarray, torch.Tensor)):
         frames = input_path
@@ -61,7 +65,7 @@ def load_video_frames(input_path, start_frame: int = 0, frame_count: int = 0, pr
         frames = frames[start_frame:end]
         if frames.shape[0] == 0:
             raise RuntimeError("No frame is loaded from the given frames")
-        return frames_from_rgb24(frames, processing_res, resample_method, device)
+        return frames_from_rgb24(frames, processing_res, resample_method, device, return_source)
     if not isinstance(input_path, (str, os.PathLike)):
         raise TypeError(f"load_video_frames: a path or uint8 [N, H, W, 3] frames, got {type(input_path)}")
     try:
@@ -84,7 +88,7 @@ def load_video_frames(input_path, start_frame: int = 0, frame_count: int = 0, pr
         container.close()
     if not frame_ls:
         raise RuntimeError(f"No frame is loaded from {input_path}")
-    return frames_from_rgb24(np.stack(frame_ls), processing_res, resample_method, device)
+    return frames_from_rgb24(np.stack(frame_ls), processing_res, resample_method, device, return_source)
 
 
 def write_video_from_numpy(frames: np.ndarray, output_path, fps: int = 30, codec=None, crf: int = 23,
