@@ -766,6 +766,49 @@ int rdmi_joint_bilateral_upsample(const void* values, int values_dtype, const fl
                                   int h, int w, int H, int W, int radius, float sigma_spatial, float sigma_range,
                                   float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Depth boundaries (since rdmi_version 12): precision / recall counts of the occluding contours of an aligned
+ * depth video against those of a target — after Depth Pro's scale-invariant boundary F1, restated from its
+ * definition.  A ramp two pixels wide costs almost nothing in AbsRel or δ₁; it costs recall here.  The reference has
+ * no counterpart.
+ *
+ * pred, target [N][H][W] contiguous, each RDMI_F16 or RDMI_F32 (any element-aligned pointer); mask [N][H][W] u8 or
+ * NULL; st [N][2] f64 in device memory as written by rdmi_depth_fit for the fit of `space`.
+ * Aligned prediction.  a = φ⁻¹(fma(s, p, t)) clamped to [clip_lo, clip_hi] with the frame's own (s, t), exactly
+ *   rdmi_depth_errors_space's value (clip bounds are doubles here); g is the target.
+ * Valid pixel.  The rule of rdmi_depth_errors_space — mask absent or ≠ 0, p and g finite, lo < g < hi, g > 0 outside
+ *   RDMI_SPACE_DEPTH, a frame whose s and t are not NaN — and in addition a finite and a > 0.
+ * Pair.  Two valid pixels that are horizontal or vertical neighbours in one frame; nothing crosses a row end or a
+ *   frame.  pairs [N][2] (out) = the frame's horizontal and vertical pairs.
+ * Edge.  thresholds [M] (HOST memory, read before the launch): 1 … RDMI_BOUNDARY_MAX_THRESHOLDS finite values > 1,
+ *   strictly rising.  Pixel i has an edge of map d in direction k — 0 R (x + 1), 1 L (x − 1), 2 D (y + 1), 3 U
+ *   (y − 1) — at τ iff its neighbour j in that direction forms a pair with it and d(j) > τ·d(i): one f64 product,
+ *   one comparison, no division; i is the near side.  The test is taken as written for every pair, also for a
+ *   target ≤ 0 (possible with lo < 0 in RDMI_SPACE_DEPTH), where it no longer says anything about a ratio.
+ * counts [N][M][4][3] (out, 64-bit) = per frame, threshold and direction: TP = #(edge of a and edge of g),
+ *   NP = #edge of a, NG = #edge of g.  A frame without a fit has zero rows.
+ * edges (NULL or out, u8 [N][H][W]) = for threshold edge_index: bits 0–3 the edge of a in R, L, D, U at this
+ *   pixel, bits 4–7 the same for g; 0 for a pixel that is not valid.  Every byte is written, by plain stores.
+ *
+ * One launch reads the operands once for all thresholds and keeps 32-bit integer histograms in LDS; each workgroup
+ * writes one row to workspace (≥ rdmi_depth_boundary_workspace(N, H, W, M) BYTES, 16-byte aligned, no
+ * initialisation needed; 0 for arguments the call would refuse) and a second small launch adds a frame's rows in
+ * 64-bit.  Integer addition is exact and order-free, so all outputs are bitwise reproducible and do not depend on
+ * N, on the other frames or on the alignment of the buffers; a pixel's aligned value comes from one function
+ * whichever pair reads it.  Nothing synchronises, allocates or uses floating-point atomics.
+ *
+ * RDMI_E_ARG before any launch: a null pred / target / st / thresholds / counts / pairs / workspace, N, H or W < 1,
+ * a dtype other than RDMI_F16 / RDMI_F32, an unknown space, lo ≥ hi, clip_lo > clip_hi (a NaN bound fails both
+ * tests), M outside 1 … RDMI_BOUNDARY_MAX_THRESHOLDS, a threshold that is not finite, not > 1 or not above the one
+ * before it, edge_index outside 0 … M − 1 when edges is given.  RDMI_E_ALIGN: workspace not 16-byte aligned.
+ * RDMI_E_UNSUPPORTED: N > 65535, or a frame of more than 2^31 − 256 eight-pixel × four-row tiles. */
+#define RDMI_BOUNDARY_MAX_THRESHOLDS 16
+long rdmi_depth_boundary_workspace(int N, int H, int W, int M);
+int rdmi_depth_boundary(const void* pred, int pred_dtype, const void* target, int target_dtype,
+                        const unsigned char* mask, int N, int H, int W, float lo, float hi, const double* st,
+                        int space, double clip_lo, double clip_hi, const double* thresholds, int M, long long* counts,
+                        long long* pairs, unsigned char* edges, int edge_index, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,8 +4,8 @@ Public surface mirrors the reference: RollingDepthPipeline / RollingDepthOutput
 (rollingdepth/rollingdepth_pipeline.py), DepthAligner (rollingdepth/depth_aligner.py) and the
 modified diffusers attention processor (CrossFrameAttnProcessor); depth_metrics / align_scale_shift
 (metrics.py) score a depth video after a least-squares scale and shift, temporal_metrics its change
-from frame to frame, optical_flow (flow.py) estimates the flow and occlusion mask that score needs from the
-RGB frames; quantiles (kernels.py) takes exact order statistics of a device tensor; guided_upsample (upsample.py)
+from frame to frame, boundary_metrics the precision and recall of its occlusion boundaries; optical_flow
+(flow.py) estimates the flow and occlusion mask the temporal score needs from the RGB frames; quantiles (kernels.py) takes exact order statistics of a device tensor; guided_upsample (upsample.py)
 brings a depth video to the frames' resolution with its edges on the image's.  All arithmetic runs in
 librdmi.so (HIP); importing the compute modules without the built library raises.
 """
@@ -22,7 +22,8 @@ def __getattr__(name):
     if name == "CrossFrameAttnProcessor":
         from .attention_processor import CrossFrameAttnProcessor
         return CrossFrameAttnProcessor
-    if name in ("depth_metrics", "align_scale_shift", "DepthMetrics", "temporal_metrics", "TemporalMetrics"):
+    if name in ("depth_metrics", "align_scale_shift", "DepthMetrics", "temporal_metrics", "TemporalMetrics",
+                "boundary_metrics", "BoundaryMetrics"):
         from . import metrics
         return getattr(metrics, name)
     if name in ("optical_flow", "OpticalFlow"):

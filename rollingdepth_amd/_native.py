@@ -15,6 +15,7 @@ vp = C.c_void_p
 i32 = C.c_int
 i64 = C.c_long
 f32 = C.c_float
+f64 = C.c_double
 
 
 class GemmArgs(C.Structure):
@@ -163,6 +164,9 @@ _SIGS = {
                                  vp, vp, vp, vp, vp]),
     "rdmi_joint_bilateral_upsample": (i32, [vp, i32, vp, vp, i32, i64, i64, i64, i64, f32, i32, i32, i32, i32, i32,
                                             i32, i32, f32, f32, vp, vp]),
+    "rdmi_depth_boundary_workspace": (i64, [i32, i32, i32, i32]),
+    "rdmi_depth_boundary": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, f32, f32, vp, i32, f64, f64, vp, i32, vp, vp,
+                                  vp, i32, vp, vp]),
 }
 
 RDMI_F16, RDMI_F32, RDMI_U8, RDMI_F32_X3, RDMI_F32_X6 = 0, 1, 2, 3, 4

@@ -1590,6 +1590,37 @@ def depth_temporal(pred: torch.Tensor, target: Optional[torch.Tensor], mask: Opt
     return sums
 
 
+BOUNDARY_MAX_THRESHOLDS = 16  # RDMI_BOUNDARY_MAX_THRESHOLDS
+
+
+def depth_boundary(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor], st: torch.Tensor, H: int,
+                   W: int, thresholds: Sequence[float], lo: float = 1e-3, hi: float = math.inf, space: int = 0,
+                   clip_lo: float = -math.inf, clip_hi: float = math.inf, edge_index: Optional[int] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Boundary counts of φ⁻¹(fma(s, pred, t)) against target (rdmi.h rdmi_depth_boundary) → (counts int64
+    [N, M, 4, 3] = TP, NP, NG per frame, threshold and direction R, L, D, U; pairs int64 [N, 2]; edges uint8 [N, H, W]
+    for thresholds[edge_index], or None when edge_index is None), all on the device.  pred, target, mask (u8 or None)
+    [N, H·W]; st f64 [N, 2]; the thresholds' checks are librdmi's."""
+    N, P = _depth_inputs(pred, target, mask, "depth_boundary")
+    if P != H * W:
+        raise ValueError(f"depth_boundary: H·W = {H}·{W} does not match pred's {P} pixels per frame")
+    _need(st, torch.float64, "depth_boundary.st")
+    if st.shape != (N, 2) or not st.is_contiguous():
+        raise ValueError(f"depth_boundary.st: contiguous [N, 2] expected, got {tuple(st.shape)}")
+    M = len(thresholds)
+    tau = (C.c_double * max(M, 1))(*thresholds)
+    dev = pred.device
+    counts = torch.empty((N, M, 4, 3), dtype=torch.int64, device=dev)
+    pairs = torch.empty((N, 2), dtype=torch.int64, device=dev)
+    edges = None if edge_index is None else torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rdmi_depth_boundary_workspace(N, H, W, M)), 16), dtype=torch.uint8, device=dev)
+    check(lib.rdmi_depth_boundary(pred.data_ptr(), _dtype_code(pred), target.data_ptr(), _dtype_code(target), _p(mask),
+                                  N, H, W, lo, hi, st.data_ptr(), space, clip_lo, clip_hi, tau, M, counts.data_ptr(),
+                                  pairs.data_ptr(), _p(edges), 0 if edge_index is None else edge_index, ws.data_ptr(),
+                                  _stream()), "rdmi_depth_boundary")
+    return counts, pairs, edges
+
+
 # ----------------------------------------------------------------------------- optical flow (pyramidal Lucas–Kanade)
 FLOW_MAX_LEVELS, FLOW_MAX_RADIUS = 5, 7  # RDMI_FLOW_MAX_LEVELS, RDMI_FLOW_MAX_RADIUS
 

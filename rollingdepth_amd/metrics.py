@@ -18,9 +18,15 @@ along an optical flow the caller supplies or that is estimated from the RGB fram
     t = temporal_metrics(pred, target, mask, frames=rgb)  # flow and occlusion mask estimated from the frames
     t.flicker, t.tge, t.change_corr
 
-All sums run in librdmi (rdmi_depth_moments / _fit / _errors / _temporal, f64, fixed summation order: the same
-inputs give the same bits on every call); this module only validates, reshapes and does the last few host
-divisions.
+boundary_metrics scores what the per-pixel errors hardly see, the occlusion boundaries: precision, recall and F1 of
+the edges of the aligned prediction — a neighbour more than τ times farther — against the target's, pixel-exact:
+
+    b = boundary_metrics(pred, target, mask)              # ten thresholds τ = 1.05 … 1.25
+    b.f1, b.precision, b.recall, b.f1_per_threshold
+
+All sums run in librdmi (rdmi_depth_moments / _fit / _errors / _temporal, f64, fixed summation order, and
+rdmi_depth_boundary, integers: the same inputs give the same bits on every call); this module only validates,
+reshapes and does the last few host divisions.
 """
 from __future__ import annotations
 
@@ -318,3 +324,143 @@ def temporal_metrics(pred: torch.Tensor, target: Optional[torch.Tensor] = None, 
     sums = K.depth_temporal(p, g, m, fl, pm, st, H, W, frame_step, lo, hi, sp, clip_lo, clip_hi, ws)
     st = st.cpu()
     return _pool_temporal(sums.cpu(), st[:, 0].contiguous(), st[:, 1].contiguous(), frame_step, g is not None)
+
+
+# numpy.linspace(1.05, 1.25, 10), bit for bit
+DEFAULT_BOUNDARY_THRESHOLDS = tuple(1.05 + (1.25 - 1.05) * i / 9 for i in range(9)) + (1.25,)
+MAX_BOUNDARY_THRESHOLDS = 16  # RDMI_BOUNDARY_MAX_THRESHOLDS
+
+
+@dataclass
+class BoundaryMetrics:
+    """Pooled over all frames with a fit: the integer counts are added over the frames, then, per threshold τ,
+    precision(τ) = ¼ Σ_k TP_k / max(NP_k, 1) and recall(τ) = ¼ Σ_k TP_k / max(NG_k, 1) over the four directions
+    k = R, L, D, U, f1(τ) = 2PR / (P + R) (0 when P + R = 0); the scalars are the per-threshold values weighted by
+    τ_m / Σ τ.  With no valid pair at all every float field is NaN."""
+    f1: float
+    precision: float
+    recall: float
+    f1_per_threshold: torch.Tensor         # f64 [M], host
+    precision_per_threshold: torch.Tensor  # f64 [M], host
+    recall_per_threshold: torch.Tensor     # f64 [M], host
+    thresholds: torch.Tensor               # f64 [M], host
+    counts: torch.Tensor   # int64 [N, M, 4, 3], host: TP, NP, NG per frame, threshold and direction R, L, D, U
+    pairs: torch.Tensor    # int64 [N, 2], host: valid horizontal and vertical pairs per frame
+    n_pairs: int
+    scale: torch.Tensor    # f64 [N], host
+    shift: torch.Tensor    # f64 [N], host
+    frames_skipped: List[int]  # frames without a fit (NaN scale / shift): their count rows are zero
+    edges: Optional[torch.Tensor]  # uint8 [N, H, W] on the device, or None
+
+
+def _boundary_thresholds(thresholds, edge_threshold) -> Tuple[List[float], int]:
+    """The checks of boundary_metrics' thresholds → (the thresholds as floats, the index of edge_threshold)."""
+    if thresholds is None:
+        tau = list(DEFAULT_BOUNDARY_THRESHOLDS)
+    else:
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.tolist()
+        try:
+            seq = list(thresholds)
+        except TypeError:
+            raise TypeError(f"thresholds: a sequence of numbers expected, got {type(thresholds).__name__}") from None
+        for v in seq:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) and not hasattr(v, "__float__"):
+                raise TypeError(f"thresholds: numbers expected, got {type(v).__name__}")
+        tau = [float(v) for v in seq]
+    if not 1 <= len(tau) <= MAX_BOUNDARY_THRESHOLDS:
+        raise ValueError(f"thresholds: 1 to {MAX_BOUNDARY_THRESHOLDS} values expected, got {len(tau)}")
+    for i, v in enumerate(tau):
+        if not (math.isfinite(v) and v > 1.0):
+            raise ValueError(f"thresholds: finite values > 1 expected, got {v} at {i}")
+        if i and not v > tau[i - 1]:
+            raise ValueError(f"thresholds: a strictly increasing sequence expected, got {v} after {tau[i - 1]}")
+    if edge_threshold is None:
+        return tau, len(tau) // 2
+    if isinstance(edge_threshold, bool) or not isinstance(edge_threshold, (int, float)):
+        raise TypeError(f"edge_threshold: a number expected, got {type(edge_threshold).__name__}")
+    if float(edge_threshold) not in tau:
+        raise ValueError(f"edge_threshold: one of the thresholds {tau} expected, got {edge_threshold}")
+    return tau, tau.index(float(edge_threshold))
+
+
+def _pool_boundary(counts: torch.Tensor, pairs: torch.Tensor, tau: List[float], scale: torch.Tensor,
+                   shift: torch.Tensor, edges: Optional[torch.Tensor]) -> BoundaryMetrics:
+    """Host tensors (int64 [N, M, 4, 3] counts, int64 [N, 2] pairs, f64 [N] scale / shift) → BoundaryMetrics: integer
+    sums over the frames, then the few f64 divisions in threshold and direction order."""
+    M = len(tau)
+    tot = counts.sum(0).tolist()  # int64: exact in any order
+    n_pairs = int(pairs.sum())
+    skipped = [f for f, (s, t) in enumerate(zip(scale.tolist(), shift.tolist())) if math.isnan(s) or math.isnan(t)]
+    nan = math.nan
+    P, R, F = [nan] * M, [nan] * M, [nan] * M
+    f1 = precision = recall = nan
+    if n_pairs > 0:
+        tau_sum = 0.0
+        for v in tau:
+            tau_sum += v
+        f1 = precision = recall = 0.0
+        for m in range(M):
+            p = r = 0.0
+            for k in range(4):
+                tp, npred, ngt = tot[m][k]
+                p += tp / max(npred, 1)
+                r += tp / max(ngt, 1)
+            P[m], R[m] = 0.25 * p, 0.25 * r
+            F[m] = 2.0 * P[m] * R[m] / (P[m] + R[m]) if P[m] + R[m] > 0.0 else 0.0
+            w = tau[m] / tau_sum
+            f1 += w * F[m]
+            precision += w * P[m]
+            recall += w * R[m]
+    f64 = lambda v: torch.tensor(v, dtype=torch.float64)
+    return BoundaryMetrics(f1=f1, precision=precision, recall=recall, f1_per_threshold=f64(F),
+                           precision_per_threshold=f64(P), recall_per_threshold=f64(R), thresholds=f64(tau),
+                           counts=counts, pairs=pairs, n_pairs=n_pairs, scale=scale, shift=shift,
+                           frames_skipped=skipped, edges=edges)
+
+
+def boundary_metrics(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                     align: str = "video", space: str = "depth", valid_range=(1e-3, math.inf),
+                     clip: Optional[Tuple[float, float]] = None, thresholds=None, return_edges: bool = False,
+                     edge_threshold: Optional[float] = None) -> BoundaryMetrics:
+    """Precision, recall and F1 of the occlusion boundaries of the aligned prediction against the target's — after
+    Depth Pro's scale-invariant boundary F1, restated from its definition.
+
+    pred, target, mask, align, space, valid_range and clip as for depth_metrics: the fit is the one depth_metrics takes
+    and a = clamp(φ⁻¹(scale·pred + shift)) is its aligned prediction.  A pixel counts when it is valid by
+    depth_metrics' rule and its a is finite and > 0 (floor with clip where the fit can go negative).  Pixel i has an
+    edge of a map d in direction R, L, D or U at threshold τ when its neighbour j there is also a valid pixel of the
+    frame and d(j) > τ·d(i): i is the near side of a depth ratio above τ, whatever the scale of d.  TP, NP and NG
+    count the pixels with an edge of both maps, of a, and of the target, per frame, threshold and direction.
+
+    Matching is pixel-exact: a contour of the prediction displaced by one pixel from the target's is a miss in both
+    precision and recall; there is no distance tolerance.
+
+    thresholds: strictly increasing, 1 to 16 finite values > 1; default numpy.linspace(1.05, 1.25, 10).
+    return_edges: also return the per-pixel edge map (uint8 [N, H, W] on the device; bits 0–3 the edge of a in R, L,
+    D, U, bits 4–7 the target's, 0 for a pixel that does not count) at edge_threshold, which must be one of the
+    thresholds and defaults to the middle one, thresholds[M // 2].  Frames without a fit are left out and listed in
+    frames_skipped.  All counting runs in librdmi (rdmi_depth_boundary: integers only, so the same inputs give the same
+    result on every call); this function adds the frames' integers and takes the last divisions in f64."""
+    if align not in ALIGN_MODES:
+        raise ValueError(f"align: one of {ALIGN_MODES} expected, got {align!r}")
+    clip_lo, clip_hi = _space_and_clip(space, clip)
+    if not isinstance(return_edges, bool):
+        raise TypeError(f"return_edges: a bool expected, got {type(return_edges).__name__}")
+    tau, edge_index = _boundary_thresholds(thresholds, edge_threshold)
+    if target is None:
+        raise TypeError("target: a tensor expected, got NoneType")
+    p, g, m, lo, hi = _prepare(pred, target, mask, valid_range)
+    from . import kernels as K
+
+    N, P = p.shape
+    H, W = pred.shape[-2], pred.shape[-1]
+    sp = K.DEPTH_SPACES[space]
+    ws = None
+    if align != "none":
+        ws = K.depth_moments(p, g, m, lo, hi, space=sp)
+    _, st = K.depth_fit(ws, N, P, K.DEPTH_FIT_MODES[align], device=p.device)
+    counts, pairs, edges = K.depth_boundary(p, g, m, st, H, W, tau, lo, hi, sp, clip_lo, clip_hi,
+                                            edge_index if return_edges else None)
+    st = st.cpu()
+    return _pool_boundary(counts.cpu(), pairs.cpu(), tau, st[:, 0].contiguous(), st[:, 1].contiguous(), edges)
