@@ -809,6 +809,56 @@ int rdmi_depth_boundary(const void* pred, int pred_dtype, const void* target, in
                         int space, double clip_lo, double clip_hi, const double* thresholds, int M, long long* counts,
                         long long* pairs, unsigned char* edges, int edge_index, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Temporal filter (since rdmi_version 13): a motion-compensated bilateral filter over time — each pixel of a depth
+ * video is averaged with the depths its neighbouring frames hold where a given flow says the pixel went, with
+ * weights that fall off with the frame distance and with the depth difference.  The flow and its occlusion mask are
+ * operands (rdmi_flow_lk_level / rdmi_flow_fb_check produce them; any other source serves).  Deterministic, no
+ * learned part; the reference has no counterpart.
+ *
+ * depth [N][H][W] contiguous, RDMI_F16 (widened exactly) or RDMI_F32: the whole video.  Output frames are
+ *   i = f0 … f0 + n − 1 (0 ≤ f0, n ≥ 1, f0 + n ≤ N); out [n][H][W] f32.
+ * Slots.  s = 0 … 2R − 1 stands for the frame offset k = −R, …, −1, +1, …, +R in that order (R = radius).
+ *   flow [2R][n][H][W][2] f32: row i − f0 of slot s holds (dx, dy) in pixels from frame i to frame i + k at the
+ *   pixels of frame i (rdmi_depth_temporal's convention).  valid [2R][n][H][W] u8, or NULL for all ones.  Row i − f0
+ *   of slot s is never read when i + k lies outside [0, N).
+ * Constants.  ct = log₂e / (2·σt²) and cd = log₂e / (2·σd²), each formed in f64 and rounded to f32 once (σt =
+ *   sigma_time in frames, σd = sigma_depth in the units of depth; the exponent is kept in base 2).
+ * Output pixel p = (x, y) of frame i.  All arithmetic is f32; every operation below is rounded once, and only where
+ *   an fma is written are a product and a sum contracted.
+ *     d0 = D_i(p).  If d0 is not finite, out = d0 and nothing else is read.
+ *     acc = +0, wsum = +0; then for the slots in ascending order whose j = i + k lies in [0, N):
+ *       1. skip if valid = 0;
+ *       2. X = (float)x + dx, Y = (float)y + dy; skip unless 0 ≤ X ≤ W − 1 and 0 ≤ Y ≤ H − 1 — a NaN fails the test,
+ *          so no address is ever formed from one;
+ *       3. x0 = min((int)X, W − 1), x1 = min(x0 + 1, W − 1), wx = X − (float)x0; y0, y1, wy alike;
+ *       4. with a00 = D_j(x0, y0), a01 = D_j(x1, y0), a10 = D_j(x0, y1), a11 = D_j(x1, y1):
+ *          t0 = fma(wx, a01 − a00, a00), t1 = fma(wx, a11 − a10, a10), d_k = fma(wy, t1 − t0, t0) — the lerp form, not
+ *          the (1 − w)·a + w·b of the flow check's bilerp: equal taps give exactly that value whatever wx and wy
+ *          are, so a constant video comes out bit for bit;
+ *       5. skip if d_k is not finite (a NaN or ∞ among the taps that the weights do not cancel);
+ *       6. δ = d_k − d0; e = fma(δ·δ, cd, (float)(k·k)·ct); w = exp2(−e), the hardware v_exp_f32 (1 ulp);
+ *       7. acc = fma(w, δ, acc); wsum = wsum + w.
+ *     out = d0 + acc / (1 + wsum), the IEEE division: the frame's own weight is the 1, so no σ gives 0/0.
+ *   Consequences: a constant video is reproduced exactly; N = 1, all-invalid neighbours and flows that all leave the
+ *   frame are the identity, bitwise; the rounding errors scale with the spread of the taps around d0, not with |d|.
+ *   Finite depths are expected to differ by less than FLT_MAX (δ finite).
+ * One launch covers all n frames and all 2R neighbours: a workgroup owns a 32 × 8 pixel tile of one output frame
+ *   (256 lanes, lanes along x), d0 is read once and out written once, the taps are element loads through the caches.
+ *   No atomics, no workspace, no allocation, nothing synchronises: graph-capturable like every other entry point.
+ *   Frame bases are 64-bit: N·H·W is not limited.  A pixel's result is one lane's chain in the fixed order above,
+ *   element by element (there is no wide path over pixels): the bits do not depend on n, on f0 (given the same depth
+ *   and the same rows of flow / valid), on the pointers' alignment, or on the call.
+ * RDMI_E_ARG before any launch: a null depth / flow / out, N, H, W or n < 1, f0 < 0 or f0 + n > N, radius outside
+ *   1 … RDMI_TFILTER_MAX_RADIUS, a depth dtype other than RDMI_F16 / RDMI_F32, a σ that is ≤ 0 or NaN or for which ct
+ *   or cd is not finite and positive in f32 (σ below about 4.6e-20 or above about 3e22).
+ * RDMI_E_ALIGN: flow not 8-byte aligned, or out not 4-byte aligned.
+ * RDMI_E_UNSUPPORTED: H·W > 2^30, or more than 2^31 − 1 tiles in the n frames. */
+#define RDMI_TFILTER_MAX_RADIUS 3
+int rdmi_temporal_filter(const void* depth, int depth_dtype, int N, int H, int W, int f0, int n, int radius,
+                         const float* flow, const unsigned char* valid, float sigma_time, float sigma_depth,
+                         float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,7 @@ _SIGS = {
     "rdmi_depth_boundary_workspace": (i64, [i32, i32, i32, i32]),
     "rdmi_depth_boundary": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, f32, f32, vp, i32, f64, f64, vp, i32, vp, vp,
                                   vp, i32, vp, vp]),
+    "rdmi_temporal_filter": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, f32, f32, vp, vp]),
 }
 
 RDMI_F16, RDMI_F32, RDMI_U8, RDMI_F32_X3, RDMI_F32_X6 = 0, 1, 2, 3, 4

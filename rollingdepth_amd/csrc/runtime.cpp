@@ -26,4 +26,4 @@ int check_launch(const char* what) {
 }  // namespace rdmi
 
 extern "C" const char* rdmi_last_error(void) { return rdmi::g_err; }
-extern "C" int rdmi_version(void) { return 12; }
+extern "C" int rdmi_version(void) { return 13; }

@@ -1792,3 +1792,41 @@ def joint_bilateral_upsample(values: torch.Tensor, guide_lo: torch.Tensor, guide
                                                 H, W, int(radius), float(sigma_spatial), float(sigma_range),
                                                 out.data_ptr(), _stream()), "rdmi_joint_bilateral_upsample")
     return out
+
+
+# ----------------------------------------------------------------------------- temporal filter
+TFILTER_MAX_RADIUS = 3  # RDMI_TFILTER_MAX_RADIUS
+
+
+def temporal_filter(depth: torch.Tensor, flow: torch.Tensor, valid: Optional[torch.Tensor], radius: int,
+                    sigma_time: float, sigma_depth: float, f0: int = 0, n: Optional[int] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rdmi_temporal_filter: depth [N, H, W] (f16 / f32, contiguous: the whole video) → f32 [n, H, W], the filtered
+    frames f0 … f0 + n − 1 (n None: all from f0 on).  flow: f32 [2·radius, n, H, W, 2] contiguous, slot s for the
+    offset k = −radius, …, −1, +1, …, +radius, row i − f0 the flow from frame i to frame i + k.  valid: uint8
+    [2·radius, n, H, W] contiguous or None (all ones)."""
+    _need_act(depth, "temporal_filter.depth")
+    _need(flow, F32, "temporal_filter.flow")
+    if depth.dim() != 3 or not depth.is_contiguous():
+        raise ValueError(f"temporal_filter.depth: contiguous [N, H, W] expected, got {tuple(depth.shape)}")
+    N, H, W = depth.shape
+    f0 = int(f0)
+    n = N - f0 if n is None else int(n)
+    radius = int(radius)
+    if flow.shape != (2 * radius, n, H, W, 2) or not flow.is_contiguous():
+        raise ValueError(f"temporal_filter.flow: contiguous {(2 * radius, n, H, W, 2)} expected, got "
+                         f"{tuple(flow.shape)}")
+    if valid is not None:
+        _need(valid, torch.uint8, "temporal_filter.valid")
+        if valid.shape != (2 * radius, n, H, W) or not valid.is_contiguous():
+            raise ValueError(f"temporal_filter.valid: contiguous {(2 * radius, n, H, W)} expected, got "
+                             f"{tuple(valid.shape)}")
+    if out is None:
+        out = torch.empty((max(n, 0), H, W), dtype=F32, device=depth.device)
+    if out.shape != (n, H, W) or out.dtype != F32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("temporal_filter: out must be a contiguous f32 [n, H, W] device tensor")
+    with _Timed("temporal_filter", 0, shape=(N, H, W, f0, n, radius)):
+        check(lib.rdmi_temporal_filter(depth.data_ptr(), _dtype_code(depth), N, H, W, f0, n, radius, flow.data_ptr(),
+                                       _p(valid), float(sigma_time), float(sigma_depth), out.data_ptr(), _stream()),
+              "rdmi_temporal_filter")
+    return out

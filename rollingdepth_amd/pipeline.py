@@ -224,6 +224,26 @@ def check_restore_method(restore_method, restore_kwargs=None) -> Tuple[str, Dict
     return restore_method, dict(kw)
 
 
+_STABILIZE_KWARGS = ("radius", "sigma_time", "sigma_depth", "flow_kwargs")
+
+
+def check_stabilize(stabilize, stabilize_kwargs=None) -> Tuple[bool, Dict]:
+    """`stabilize` must be a bool (TypeError otherwise) and `stabilize_kwargs` None or a dict with keys among radius,
+    sigma_time, sigma_depth and flow_kwargs (ValueError otherwise), whose values stabilize.check_stabilize_params
+    accepts: all before any device work.  Returns the flag and the keywords as a dict."""
+    if not isinstance(stabilize, bool):
+        raise TypeError(f"stabilize must be a bool, got {type(stabilize).__name__}")
+    kw = {} if stabilize_kwargs is None else stabilize_kwargs
+    if not isinstance(kw, dict) or any(k not in _STABILIZE_KWARGS for k in kw):
+        raise ValueError(f"stabilize_kwargs must be None or a dict with keys among {_STABILIZE_KWARGS}, got "
+                         f"{stabilize_kwargs!r}")
+    if kw and not stabilize:
+        raise ValueError("stabilize_kwargs belong to stabilize=True")
+    from .stabilize import check_stabilize_params
+    check_stabilize_params(**kw)
+    return stabilize, dict(kw)
+
+
 class RollingDepthPipeline:
     rgb_latent_scale_factor = 0.18215
     depth_latent_scale_factor = 0.18215
@@ -621,7 +641,8 @@ class RollingDepthPipeline:
                  restore_res: bool = False, input_fg_video_path=None, refine_stride: int = 1,
                  output_uncertainty: bool = False, merge: str = "mean",
                  renorm_percentiles: Optional[Tuple[float, float]] = None, restore_method: str = "resize",
-                 restore_kwargs: Optional[Dict] = None, **kw) -> RollingDepthOutput:
+                 restore_kwargs: Optional[Dict] = None, stabilize: bool = False,
+                 stabilize_kwargs: Optional[Dict] = None, **kw) -> RollingDepthOutput:
         """rollingdepth_pipeline.py:78-176.  `input_video_path` (or the fork's `input_fg_video_path`):
         a video file (decoding needs PyAV, absent from this image), decoded uint8 rgb24 frames
         [N, H, W, 3] (numpy / torch: resized to processing_res and normalised on the device,
@@ -637,12 +658,21 @@ class RollingDepthPipeline:
         edges land on image edges instead of becoming ramps; input_rgb is resized as before.  It needs restore_res
         and a video no smaller than the processing resolution in either dimension (ValueError before any
         inference), and it keeps the decoded uint8 frames on the device from ingest to restore: 500 frames of
-        1080p are 3.1 GB, beside what the large-resolution warning below is about."""
+        1080p are 3.1 GB, beside what the large-resolution warning below is about.
+        `stabilize` (the build's own, a bool; anything else is a TypeError): depth_pred is replaced by
+        stabilize.temporal_filter(depth_pred, frames=the processing-resolution frames of this call,
+        **stabilize_kwargs) — a motion-compensated filter over time (`stabilize_kwargs`: its radius, sigma_time,
+        sigma_depth, flow_kwargs; unknown keys and bad values are errors before any inference).  It acts at
+        processing resolution, after forward() and before restore_res, which then restores the filtered map
+        with either restore_method.  depth_coaligned, depth_uncertainty (which still describes the co-aligned
+        stage), snippet_ls and input_rgb are left as they are.  stabilize=False adds no work and changes no bit.
+        Sharded, every rank filters its assembled copy."""
         check_refine_stride(refine_stride, refine_snippet_len)
         check_output_uncertainty(output_uncertainty)
         check_merge(merge)
         check_renorm_percentiles(renorm_percentiles)
         restore_method, restore_kwargs = check_restore_method(restore_method, restore_kwargs)
+        stabilize, stabilize_kwargs = check_stabilize(stabilize, stabilize_kwargs)
         guided = restore_method == "joint_bilateral"
         if guided and not restore_res:
             raise ValueError('restore_method="joint_bilateral" needs restore_res=True')
@@ -681,6 +711,10 @@ class RollingDepthPipeline:
                            **(dict(merge=merge) if merge != "mean" else {}),
                            **(dict(renorm_percentiles=renorm_percentiles) if renorm_percentiles is not None else {}),
                            **kw)
+        if stabilize:  # at processing resolution, before any restore: the restore then acts on the filtered map
+            from .stabilize import temporal_filter
+            out.depth_pred = temporal_filter(out.depth_pred, frames=(frames if frames.dim() == 4 else frames[0]),
+                                             **stabilize_kwargs)
         if restore_res:  # rollingdepth_pipeline.py:155-173 (torchvision resize, antialias=True), on the device
             maps = ("depth_pred",) + (("depth_uncertainty",) if output_uncertainty else ())
             for name in ("input_rgb",) + (() if guided else maps):
